@@ -8,7 +8,20 @@ CSR row gather + densify, encoder/decoder forward, likelihood + KL + ELBO,
 backward, (gradient all-reduce), clip + Adam.  Inputs (the CSR matrix) are
 resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+``--dump-outputs DIR`` writes, as float32 ``DIR/<name>.npy``, what one more step
+of the timed path (``Workload.one_step`` on the same plan, in the configuration
+the timed steps ran, after the result line is printed) leaves to its caller
+when it starts from inputs that are the same in every run: the state the
+workload was built in and its first minibatch and noise.  Why not the last
+timed step itself: the timed steps train on, the decoder gradient's default
+sums (fp32 atomics) differ from run to run in their last bits, Adam turns such
+a difference in a near-zero gradient into up to a learning-rate step, and over
+many steps two runs drift apart by far more than rounding -- the last timed
+step has no fixed inputs.  Two dumps of that one step differ by the rounding
+of the atomic sums (bit for bit under ``--dd-slabs``), and, where a gradient
+lies within Adam's epsilon of zero, by its effect on the update.
 
 For N > 1 the script starts one rank per GPU itself (it re-executes under
 ``python -m torch.distributed.run --nproc-per-node N``, rendezvous on
@@ -46,13 +59,26 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense (MI355X_MICROARCH.md); the exact nine-te
                                 # fp32 product costs nine bf16 MFMAs: 2500 / 9 = 277.8 TFLOP/s
 PEAK_HBM_GBS = 8000.0
 MIN_WARM_SECONDS = 1.0          # real steps before the timed window, whatever --warmup says
+PROBE_MAX_STEPS = 4096          # event pairs scvae_plan_probe_heads arms at most
+DUMP_MAX_ELEMENTS = 1 << 22     # --dump-outputs: per array (16 MB of float32; four arrays)
+
+
+def positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError("at least 1 expected, got {}".format(value))
+    return value
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=positive_int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what one more step of the timed path computes from the built "
+                         "state and the first minibatch (scalars, parameters after its "
+                         "optimiser update, gradients, moving statistics) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=4096,
                     help="cells per GPU per step (weak scaling) / cells per step over all "
                          "GPUs (strong scaling)")
@@ -590,7 +616,8 @@ class Workload:
                  for _ in range(steps)] if self.sync is not None else None)
         # HIP events around the dominant kernel of every timed step, on the step's stream
         # (scvae_plan_probe_heads): the `roofline` of the line is measured inside the region
-        self.engine.probe_heads(steps)
+        # (the plan arms at most PROBE_MAX_STEPS; later steps run unprobed)
+        self.engine.probe_heads(min(steps, PROBE_MAX_STEPS))
         barrier()
         t0 = time.perf_counter()
         events[0].record()
@@ -612,6 +639,50 @@ class Workload:
         per_step = [events[i].elapsed_time(events[i + 1]) for i in range(steps)]
         self.exposed_comm_ms = ([a.elapsed_time(b) for a, b in comm] if comm else [])
         return elapsed, per_step, warm_steps
+
+    def step_from_built_state(self):
+        """One step of the timed path, in its configuration, on inputs that are
+        the same in every run: the engine re-initialised as it was built (seed
+        0), the minibatch and noise streams back at their start.  Returns
+        {name: float32 array} on the host (``dump_sample``): the scalars of the
+        step (include/scvae_hip.h; data parallel: summed over the ranks, as the
+        result line's), the parameters after its optimiser update, its
+        gradients and the moving statistics.  Every rank takes the step (data
+        parallel: the gradient all-reduce)."""
+        e = self.engine
+        e.initialise(0)
+        e.scalars.zero_()
+        self.generator.manual_seed(2)
+        self.perm = self._permutation()
+        self.cursor = 0
+        self.step_counter = 0
+        self.slot = 0
+        self.primed = False
+        self.one_step()
+        scalars = e.scalars.clone()
+        if self.sync is not None:
+            self.sync.all_reduce_scalars(scalars)
+        self.torch.cuda.synchronize(self.device)
+        return {name: dump_sample(tensor.detach().float().cpu().numpy())
+                for name, tensor in (("scalars", scalars), ("parameters", e.params),
+                                     ("gradients", e.grads), ("moving_statistics", e.moving))}
+
+
+def dump_sample(a):
+    """``a`` itself, or -- more than DUMP_MAX_ELEMENTS elements -- a fixed sample
+    of that many (seeded positions, in order; the same for arrays of one size)."""
+    import numpy
+    if a.size <= DUMP_MAX_ELEMENTS:
+        return a
+    return a[numpy.sort(numpy.random.default_rng(0).choice(
+        a.size, DUMP_MAX_ELEMENTS, replace=False))]
+
+
+def dump_outputs(directory, outputs):
+    import numpy
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        numpy.save(os.path.join(directory, name + ".npy"), a)
 
 
 def describe(cells, F, likelihood, gm, K, L):
@@ -1054,6 +1125,10 @@ def main():
         if world == 1 and not args.no_cpu_baseline and headline:
             result["cpu_baseline"] = cpu_baseline(matrix, B)
         print(json.dumps(result), flush=True)
+    if args.dump_outputs is not None:
+        outputs = work.step_from_built_state()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     if world > 1:
         dist.barrier()
         from scvae_amd.dataparallel import release_gradient_groups

@@ -432,3 +432,99 @@ def test_six_term_heads_are_fp32_class(cuda_device):
         assert errs["bf16x6"][k] <= max(2.0 * errs["fp32"][k], 2e-7), (k, errs)
         assert errs["bf16x9"][k] <= max(2.0 * errs["fp32"][k], 2e-7), (k, errs)
     print("max-norm relative errors against fp64:", errs)
+
+
+def _adam_first_step(p0, g, lr):
+    """Parameters after the first clip + Adam step from zeroed moments (fp64)."""
+    return om.clip_and_adam({"p": p0}, {"p": g}, om.adam_state({"p": p0}), lr)["p"]
+
+
+def _same_step(a, b, p0, lr, what):
+    """Two dumps of one training step from the same inputs (float32 arrays by
+    name; ``p0`` the parameters before the step at the same positions): the
+    forward's scalars and moving statistics to fp32 rounding, the gradients to
+    the rounding of differently ordered sums, and the parameters -- Adam moves
+    each by lr g / (|g| + eps_hat), which near g = 0 magnifies the rounding of
+    g -- the same where |g| > 100 eps_hat, and everywhere the optimiser applied
+    to each dump's own gradient, moved by no more than lr."""
+    def close(x, y, rtol, name):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        err = np.abs(x - y).max() / max(np.abs(y).max(), 1e-30)
+        assert err <= rtol, (what, name, err)
+    close(a["scalars"], b["scalars"], 1e-6, "scalars")
+    close(a["moving_statistics"], b["moving_statistics"], 1e-6, "moving statistics")
+    close(a["gradients"], b["gradients"], 1e-5, "gradients")
+    eps_hat = om.ADAM_EPSILON / np.sqrt(1.0 - om.ADAM_BETA2)
+    far = np.abs(a["gradients"].astype(np.float64)) > 100 * eps_hat
+    assert far.any(), what
+    close(a["parameters"][far], b["parameters"][far], 1e-6, "parameters")
+    p0 = torch.from_numpy(p0).double()
+    for d in (a, b):
+        moved = np.abs(d["parameters"] - p0.numpy()).max()
+        assert 0.5 * lr < moved <= 1.001 * lr, (what, moved)
+        own = _adam_first_step(p0, torch.from_numpy(d["gradients"]).double(), lr)
+        close(d["parameters"], own.numpy(), 1e-6, "parameters vs Adam on own gradient")
+
+
+def test_bench_dumps_a_step_of_the_timed_path_on_fixed_inputs(tmp_path, cuda_device):
+    """``bench.py --dump-outputs DIR``: one more step of the timed path, in its
+    configuration (the library's default fp32 atomics for dd), from the built
+    state and the first minibatch, as float32 ``.npy`` files within 64 MB; the
+    result line reports the ``--steps`` it was given.  Two runs -- warm-ups of
+    different lengths -- dump the same step to rounding (``_same_step``), and
+    so does the step taken here through ``Engine.step`` on the same minibatch
+    (fetched as fp32 instead of uint16) and noise."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from scvae_amd.engine import Engine
+    from scvae_amd.minibatch import philox_normal_blocks, synthetic_count_matrix
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cells, B, lr = 8192, 4096, 1e-4
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        directory = tmp_path / run
+        out = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+             "--cells", str(cells), "--batch", str(B), "--steps", "5", "--warmup", "2",
+             "--no-cpu-baseline", "--no-other-workloads",
+             "--dump-outputs", str(directory)],
+            cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads(
+            [l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({p.stem: np.load(p) for p in sorted(directory.glob("*.npy"))})
+    for r in lines:
+        assert r["steps"] == 5 and r["ms_per_step"] > 0
+        assert r["dd_accumulation"].startswith("xcd-local fp32 atomics")
+    a, b = dumps
+    assert set(a) == {"scalars", "parameters", "gradients", "moving_statistics"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all(), name
+
+    # the same step here: the bench's matrix, first rows and noise (Workload)
+    matrix, _ = synthetic_count_matrix(cells, bench.N_FEATURES, density=0.05, seed=60,
+                                       device=cuda_device)
+    eng = Engine(bench.N_FEATURES, bench.LATENT, bench.HIDDEN, bench.LIKELIHOOD,
+                 batch_norm=True, device=cuda_device, seed=0)
+    assert eng.dd_atomics
+    p0 = bench.dump_sample(eng.params.cpu().numpy())
+    rows = torch.randperm(matrix.number_of_rows, device=cuda_device,
+                          generator=torch.Generator(device=cuda_device).manual_seed(2))[:B]
+    x = torch.empty(B, bench.N_FEATURES, device=cuda_device)
+    rc = torch.empty(B, device=cuda_device)
+    matrix.request(rows, x, rc).issue()
+    eps = torch.empty(1, B, bench.LATENT, device=cuda_device)
+    philox_normal_blocks(eps, block_stride=B, row_offset=0, seed=1, stream_id=0)
+    eng.step(x, x, eps=eps, row_const=rc, training=True, global_cells=B,
+             x_counts=matrix.integer_counts, learning_rate=lr)
+    torch.cuda.synchronize()
+    here = {name: bench.dump_sample(t.cpu().numpy()) for name, t in (
+        ("scalars", eng.scalars), ("parameters", eng.params),
+        ("gradients", eng.grads), ("moving_statistics", eng.moving))}
+    assert here["scalars"][0] < 0
+    _same_step(a, b, p0, lr, "two runs")
+    _same_step(a, here, p0, lr, "run against Engine.step")

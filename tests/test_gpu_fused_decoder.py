@@ -107,6 +107,42 @@ def test_hidden_sizes(cuda_device, H):
     _run(cuda_device, "zero-inflated negative binomial", 40, 40, 90, H, 0.2)
 
 
+def _refused_on_fp32(device, H, rows=64, F=150):
+    """A call asking for the fp32 kernels at a width they do not take is
+    refused before anything is launched (no silent change of arithmetic), for
+    training and forward-only calls, and leaves its outputs as they were."""
+    from scvae_amd import _lib
+    lib = _lib.load()
+    for name in ("negative binomial", "zero-inflated negative binomial"):
+        kind, heads = _lib.LIKELIHOOD_KINDS[name]
+        assert lib.scvae_decoder_train_kernel(kind, H, 0) == 0
+        P = len(heads)
+        g = torch.Generator(device=device).manual_seed(H)
+        d = torch.rand(rows, H, device=device, generator=g)
+        W = [torch.rand(H, F, device=device, generator=g) for _ in range(P)]
+        b = [torch.rand(F, device=device, generator=g) for _ in range(P)]
+        dW = [torch.full_like(w, 7.0) for w in W]
+        db = [torch.full_like(v, 7.0) for v in b]
+        t = torch.ones(rows, F, device=device)
+        gw = torch.ones(rows, device=device)
+        ll = torch.full((rows,), 7.0, device=device)
+        dd = torch.full((rows, H), 7.0, device=device)
+        ws = torch.empty(lib.scvae_decoder_fused_workspace_bytes(rows, H, F),
+                         dtype=torch.uint8, device=device)
+        arr = lambda ts: (ctypes.c_void_p * len(ts))(*[x.data_ptr() for x in ts])
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for train in (0, 1):
+            with pytest.raises(_lib.HipLibraryError, match="bad argument"):
+                _lib.check(lib.scvae_decoder_fused(
+                    kind, train | _lib.HEADS_FP32, d.data_ptr(), rows, H, arr(W),
+                    arr(b), arr(dW), arr(db), F, t.data_ptr(), rows,
+                    gw.data_ptr(), None, ll.data_ptr(), dd.data_ptr(),
+                    ws.data_ptr(), stream), "scvae_decoder_fused")
+        torch.cuda.synchronize()
+        for out in [ll, dd] + dW + db:
+            assert bool((out == 7.0).all())
+
+
 @pytest.mark.parametrize("H", [111, 126, 127, 128, 129, 160, 192, 200, 224, 255, 256])
 def test_wide_and_odd_hidden_sizes(cuda_device, H, head_arith):
     """``-H`` beyond the all-in-one-phase kernels' LDS budget (mu:81-126 takes any
@@ -118,9 +154,10 @@ def test_wide_and_odd_hidden_sizes(cuda_device, H, head_arith):
     step; mode 0 of ``_run``)."""
     from scvae_amd import _lib
     lib = _lib.load()
-    if head_arith == "fp32":
-        assert H > 126 or H % 2 == 0 or lib.scvae_decoder_train_kernel(1, H, 0) == 0
-        pytest.skip("the fp32 kernels stop at even H <= 126")
+    if head_arith == "fp32" and lib.scvae_decoder_train_kernel(1, H, 0) == 0:
+        assert H > 126 or H % 2     # the fp32 kernels take even H <= 126
+        _refused_on_fp32(cuda_device, H)
+        return
     assert lib.scvae_decoder_train_kernel(1, H, 1) == 3
     _run(cuda_device, "negative binomial", 200, 200, 150, H, 0.2)
     _run(cuda_device, "poisson", 70, 70, 130, H, 0.2)
