@@ -8,7 +8,7 @@ CSR row gather + densify, encoder/decoder forward, likelihood + KL + ELBO,
 backward, (gradient all-reduce), clip + Adam.  Inputs (the CSR matrix) are
 resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 ``--dump-outputs DIR`` writes, as float32 ``DIR/<name>.npy``, what one more step
 of the timed path (``Workload.one_step`` on the same plan, in the configuration
@@ -29,11 +29,18 @@ For N > 1 the script starts one rank per GPU itself (it re-executes under
 ``python bench.py --gpus 8`` and ``python -m torch.distributed.run ... bench.py
 --gpus 8`` work.  Ranks talk over RCCL (torch backend "nccl").
 
-Prints ONE JSON line on rank 0 (contract in the task description) with extra
-objects: ``roofline`` (dominant kernel vs the fp32-MFMA peak, timed live with
-HIP events), ``cpu_baseline`` (the torch-CPU fp32 port of the same step,
-``oracle/``, on the host cores; rank 0, N = 1 only) and ``other_workloads``
-(the other BASELINE.json configurations' models measured in the same run).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain
+run does only what that line's headline needs: it sets up, warms up, times the
+K steps, writes the dump if asked and prints the line.  ``--full`` adds the
+rest of the measurements to the same run, after the timed steps: ``gpu_clocks``
+(rocm-smi during the warm-up), ``roofline`` (dominant kernel vs its matrix
+cores' peak, timed live with HIP events inside the timed steps and standalone),
+``roofline_fp32_kernel``, ``roofline_hbm`` (the HBM-bound stages, ten further
+steps), ``other_workloads`` (the other BASELINE.json configurations' models,
+evaluation step, ``model.train`` epochs) and ``cpu_baseline`` (the torch-CPU
+fp32 port of the same step, ``oracle/``, on the host cores); the last two
+for N = 1 and the headline model only, each of them left out by its
+``--no-*`` option.
 """
 
 import argparse
@@ -87,12 +94,18 @@ def parse_args():
                          "split evenly over the ranks")
     ap.add_argument("--cells", type=int, default=N_CELLS)
     ap.add_argument("--features", type=int, default=N_FEATURES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: "
+                         "GPU clocks, rooflines of the dominant kernel and of the HBM-bound "
+                         "stages, the other workloads and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--dd-slabs", action="store_true",
                     help="accumulate the decoder gradient dd through per-strip slabs and a "
                          "fixed-order reduce (bit-repeatable; `scvae train --deterministic`) "
                          "instead of XCD-local fp32 atomics, the library's default")
-    ap.add_argument("--no-other-workloads", action="store_true")
+    ap.add_argument("--no-other-workloads", action="store_true",
+                    help="--full without the other workloads")
     ap.add_argument("--head-arith", default=None, choices=["fp32", "bf16x9", "bf16x6"],
                     help="arithmetic of the fused head kernels (default: the library's, "
                          "the exact nine-term bf16 split)")
@@ -301,6 +314,34 @@ def _measured_traffic(rows, F, H, kernel, targets="f32"):
     return None
 
 
+def head_kernel(engine, rows, u16=False, arith=None):
+    """The decoder-head training kernel a step of ``rows`` rows launches, asked of
+    the library without launching it: (its name as rocprofv3 prints it, its
+    arithmetic, the peak TFLOP/s of that arithmetic).  ``u16`` and ``arith`` as
+    for ``time_dominant_kernel``."""
+    from scvae_amd import _lib
+    lib = engine.lib
+    H = engine.hidden_sizes[0]
+    kind, heads = _lib.LIKELIHOOD_KINDS[engine.likelihood]
+    if arith is None:
+        arith = {"fp32": 0, "bf16x9": 1, "bf16x6": 2}[engine.head_arith]
+    which = lib.scvae_decoder_train_kernel(kind, H, arith)
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(lib.scvae_decoder_train_kernel_name(kind, H, rows, arith, 1 if u16 else 0,
+                                                   buf, 128),
+               "scvae_decoder_train_kernel_name")
+    kernel = buf.value.decode()
+    if which == 3 and arith == 2 and ", 6>" in kernel:
+        # (six of the nine terms: the roof of THAT arithmetic; the nine-term roof beside it)
+        return kernel, "bf16x6", PEAK_BF16_MFMA_TFLOPS / 6.0
+    if which == 3:
+        return kernel, "bf16x9-exact", PEAK_BF16_MFMA_TFLOPS / 9.0
+    if which == 2:
+        rem = len(heads) <= 2 and 96 < H <= 111 and rows >= 512
+        kernel = "decoder_head2_kernel<{}, true, {}>".format(kind, "true" if rem else "false")
+    return kernel, "f32", PEAK_FP32_MFMA_TFLOPS
+
+
 def time_dominant_kernel(engine, rows, launches=10, u16=False, arith=None):
     """Average duration (HIP events on the launch stream) of the dominant
     kernel of the step -- the fused decoder-head kernel -- run standalone on
@@ -361,12 +402,6 @@ def time_dominant_kernel(engine, rows, launches=10, u16=False, arith=None):
             kind, 3 | flag, d.data_ptr(), rows, H, aW, ab, adW, adb, F, t.data_ptr(),
             rows, gw.data_ptr(), rc.data_ptr(), ll.data_ptr(), dd.data_ptr(),
             ws.data_ptr(), stream), "scvae_decoder_fused")
-    which = lib.scvae_decoder_train_kernel(kind, H, arith)
-    buf = ctypes.create_string_buffer(128)
-    _lib.check(lib.scvae_decoder_train_kernel_name(kind, H, rows, arith, 1 if u16 else 0,
-                                                   buf, 128),
-               "scvae_decoder_train_kernel_name")
-    kernel = buf.value.decode()
     for _ in range(3):
         launch()
     torch.cuda.synchronize(dev)
@@ -379,18 +414,7 @@ def time_dominant_kernel(engine, rows, launches=10, u16=False, arith=None):
     seconds = start.elapsed_time(stop) / 1e3 / launches
     # algorithmic flops of the decoder heads: forward + dW + dX, 2 flop / MAC
     flops = 2.0 * rows * F * P * 3 * H
-    # the instantiation as rocprofv3 prints it
-    if which == 3 and arith == 2 and ", 6>" in kernel:
-        # (six of the nine terms: the roof of THAT arithmetic; the nine-term roof beside it)
-        peak, arith_name = PEAK_BF16_MFMA_TFLOPS / 6.0, "bf16x6"
-    elif which == 3:
-        peak, arith_name = PEAK_BF16_MFMA_TFLOPS / 9.0, "bf16x9-exact"
-    else:
-        if which == 2:
-            rem = P <= 2 and 96 < H <= 111 and rows >= 512
-            kernel = "decoder_head2_kernel<{}, true, {}>".format(
-                kind, "true" if rem else "false")
-        peak, arith_name = PEAK_FP32_MFMA_TFLOPS, "f32"
+    kernel, arith_name, peak = head_kernel(engine, rows, u16=u16, arith=arith)
     return {
         "kernel": "{} (X_TILDE heads + likelihood + dW/db/dd, "
                   "[rows,{}]x[{},{}]x{} heads)".format(kernel, H, H, F, P),
@@ -584,12 +608,14 @@ class Workload:
             self.engine.adam_step(1e-4)
         self.slot = nxt
 
-    def run(self, steps, warmup, barrier, min_warm_seconds=MIN_WARM_SECONDS):
+    def run(self, steps, warmup, barrier, min_warm_seconds=MIN_WARM_SECONDS, stage_steps=10):
         """Warm up (>= warmup steps and >= min_warm_seconds of real steps; the
         number of steps is agreed over the ranks by running in chunks between
         barriers), then time exactly ``steps`` steps between barrier + device
         synchronisation.  Per-step durations come from HIP events on the
-        launch stream (no synchronisation inside the window)."""
+        launch stream (no synchronisation inside the window).  ``stage_steps``
+        further steps behind the timed ones probe the HBM-bound stages
+        (``stage_us``; 0: none)."""
         torch = self.torch
         for _ in range(warmup):
             self.one_step()
@@ -616,7 +642,8 @@ class Workload:
                  for _ in range(steps)] if self.sync is not None else None)
         # HIP events around the dominant kernel of every timed step, on the step's stream
         # (scvae_plan_probe_heads): the `roofline` of the line is measured inside the region
-        # (the plan arms at most PROBE_MAX_STEPS; later steps run unprobed)
+        # (the plan arms at most PROBE_MAX_STEPS; later steps run unprobed).  Armed with or
+        # without --full, so that the timed steps are the same in both
         self.engine.probe_heads(min(steps, PROBE_MAX_STEPS))
         barrier()
         t0 = time.perf_counter()
@@ -628,14 +655,16 @@ class Workload:
         elapsed = time.perf_counter() - t0
         self.head_kernel_ms = self.engine.probe_heads_ms()
         self.engine.probe_heads(0)
-        # ... and, in ten further steps OUTSIDE the timed region (ten more event records per step
+        # ... and, in further steps OUTSIDE the timed region (ten more event records per step
         # would cost the headline about half a percent), around the step's HBM-bound stages
-        self.engine.probe_stages(10)
-        for _ in range(10):
-            self.one_step()
-        barrier()
-        self.stage_us = self.engine.probe_stages_us()
-        self.engine.probe_stages(0)
+        self.stage_us = {}
+        if stage_steps:
+            self.engine.probe_stages(stage_steps)
+            for _ in range(stage_steps):
+                self.one_step()
+            barrier()
+            self.stage_us = self.engine.probe_stages_us()
+            self.engine.probe_stages(0)
         per_step = [events[i].elapsed_time(events[i + 1]) for i in range(steps)]
         self.exposed_comm_ms = ([a.elapsed_time(b) for a, b in comm] if comm else [])
         return elapsed, per_step, warm_steps
@@ -941,6 +970,43 @@ def other_workloads(matrix, device, barrier):
     return out
 
 
+def full_measurements(result, args, work, matrix, device, barrier, clocks):
+    """``--full`` (rank 0): what the headline figure does not need, added to the
+    result line -- the GPU clocks, the rooflines of the dominant kernel and of the
+    HBM-bound stages, the other workloads and the CPU baseline."""
+    engine, B, K = work.engine, work.B, work.K
+    gm = work.gm
+    result["gpu_clocks"] = clocks
+    result["roofline"] = time_dominant_kernel(engine, B * K, u16=work.u16)
+    in_step = getattr(work, "head_kernel_ms", [])
+    if in_step:
+        # the same kernel timed INSIDE the timed steps (HIP events on the launch stream
+        # around every launch): this is the figure rocprofv3's per-kernel average of the
+        # same command agrees with; the standalone loop above stays for comparison
+        roof = result["roofline"]
+        seconds = sum(in_step) / len(in_step) / 1e3
+        flops = roof["algorithmic_flop_per_launch"]
+        roof["launch_us_standalone"] = roof["launch_us"]
+        roof["launch_us"] = seconds * 1e6
+        roof["launches_timed"] = len(in_step)
+        roof["achieved"] = flops / seconds / 1e12
+        roof["frac"] = roof["achieved"] / roof["peak"]
+        roof["frac_of_fp32_mfma_peak"] = roof["achieved"] / PEAK_FP32_MFMA_TFLOPS
+        roof["frac_of_bf16x9_roof"] = roof["achieved"] / (PEAK_BF16_MFMA_TFLOPS / 9.0)
+    if result["roofline"]["arith"] != "f32":
+        # the fp32-MFMA kernel on the same shapes, for comparison (not what the step ran)
+        result["roofline_fp32_kernel"] = time_dominant_kernel(
+            engine, B * K, u16=work.u16, arith=0)
+    headline = (not gm and args.likelihood == LIKELIHOOD and args.latent == LATENT)
+    if not gm:
+        # the HBM-bound kernels of the step (SURVEY.md section 8d: achieved bytes / peak)
+        result["roofline_hbm"] = hbm_rooflines(work, matrix, B)
+    if work.world == 1 and headline and not args.no_other_workloads:
+        result["other_workloads"] = other_workloads(matrix, device, barrier)
+    if work.world == 1 and not args.no_cpu_baseline and headline:
+        result["cpu_baseline"] = cpu_baseline(matrix, B)
+
+
 def main():
     global DD_ATOMICS
     args = parse_args()
@@ -1005,8 +1071,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
-    clock_probe = GpuClocks() if rank == 0 else None
-    elapsed, per_step, warm_steps = work.run(args.steps, args.warmup, barrier)
+    clock_probe = GpuClocks() if rank == 0 and args.full else None
+    elapsed, per_step, warm_steps = work.run(args.steps, args.warmup, barrier,
+                                             stage_steps=10 if args.full else 0)
     clocks = clock_probe.read() if clock_probe else None
     if world > 1:
         tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -1086,44 +1153,18 @@ def main():
             "step_mfma_frac": value / world * flops_cell / 1e12
             / PEAK_FP32_MFMA_TFLOPS,
             "last_lower_bound": lower_bound,
-            "gpu_clocks": clocks,
         }
         if gm:   # informational run: per-cell flops of the VAE formula do not apply
             result["train_flop_per_cell"] = None
             result["step_mfma_frac"] = None
-        result["roofline"] = time_dominant_kernel(engine, B * K, u16=work.u16)
-        in_step = getattr(work, "head_kernel_ms", [])
-        if in_step:
-            # the same kernel timed INSIDE the timed steps (HIP events on the launch stream
-            # around every launch): this is the figure rocprofv3's per-kernel average of the
-            # same command agrees with; the standalone loop above stays for comparison
-            roof = result["roofline"]
-            seconds = sum(in_step) / len(in_step) / 1e3
-            flops = roof["algorithmic_flop_per_launch"]
-            roof["launch_us_standalone"] = roof["launch_us"]
-            roof["launch_us"] = seconds * 1e6
-            roof["launches_timed"] = len(in_step)
-            roof["achieved"] = flops / seconds / 1e12
-            roof["frac"] = roof["achieved"] / roof["peak"]
-            roof["frac_of_fp32_mfma_peak"] = roof["achieved"] / PEAK_FP32_MFMA_TFLOPS
-            roof["frac_of_bf16x9_roof"] = roof["achieved"] / (PEAK_BF16_MFMA_TFLOPS / 9.0)
         # arithmetic of the decoder heads' three products in the training kernel
-        result["decoder_head_arith"] = result["roofline"]["arith"]
-        if result["roofline"]["arith"] != "f32":
+        result["decoder_head_arith"] = head_kernel(engine, B * K, u16=work.u16)[1]
+        if result["decoder_head_arith"] != "f32":
             # (the arithmetic type the path computes in: fp32 values, fp32 accumulation; the
             #  heads' products are issued as exact bf16 terms on the bf16 matrix cores)
-            result["dtype"] = "f32 ({} heads)".format(result["roofline"]["arith"])
-            # the fp32-MFMA kernel on the same shapes, for comparison (not what the step ran)
-            result["roofline_fp32_kernel"] = time_dominant_kernel(
-                engine, B * K, u16=work.u16, arith=0)
-        headline = (not gm and args.likelihood == LIKELIHOOD and L == LATENT)
-        if rank == 0 and not gm:
-            # the HBM-bound kernels of the step (achieved bytes / peak)
-            result["roofline_hbm"] = hbm_rooflines(work, matrix, B)
-        if world == 1 and headline and not args.no_other_workloads:
-            result["other_workloads"] = other_workloads(matrix, device, barrier)
-        if world == 1 and not args.no_cpu_baseline and headline:
-            result["cpu_baseline"] = cpu_baseline(matrix, B)
+            result["dtype"] = "f32 ({} heads)".format(result["decoder_head_arith"])
+        if args.full:
+            full_measurements(result, args, work, matrix, device, barrier, clocks)
         print(json.dumps(result), flush=True)
     if args.dump_outputs is not None:
         outputs = work.step_from_built_state()

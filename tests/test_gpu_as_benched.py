@@ -528,3 +528,39 @@ def test_bench_dumps_a_step_of_the_timed_path_on_fixed_inputs(tmp_path, cuda_dev
     assert here["scalars"][0] < 0
     _same_step(a, b, p0, lr, "two runs")
     _same_step(a, here, p0, lr, "run against Engine.step")
+
+
+def test_bench_full_adds_its_measurements_to_the_same_line(cuda_device):
+    """A plain ``bench.py`` line carries the headline and what it is made of;
+    ``--full`` adds, after the same timed steps, the GPU clocks, the dominant
+    kernel's roofline (inside the timed steps and standalone, beside the
+    fp32-MFMA kernel's) and the HBM-bound stages' -- the headline's own fields
+    say the same in both."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode, extra in (("plain", []),
+                        ("full", ["--full", "--no-cpu-baseline", "--no-other-workloads"])):
+        out = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+             "--cells", "8192", "--steps", "5", "--warmup", "2"] + extra,
+            cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[mode] = json.loads(
+            [l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    extras = {"gpu_clocks", "roofline", "roofline_fp32_kernel", "roofline_hbm"}
+    assert not (extras | {"other_workloads", "cpu_baseline"}) & set(plain)
+    assert extras <= set(full)
+    assert "other_workloads" not in full and "cpu_baseline" not in full
+    for key in ("metric", "unit", "higher_is_better", "dtype", "decoder_head_arith",
+                "minibatch_storage", "dd_accumulation", "steps", "warmup"):
+        assert plain[key] == full[key], key
+    for r in (plain, full):
+        assert r["value"] > 0 and r["ms_per_step"] > 0 and r["last_lower_bound"] < 0
+    assert full["roofline"]["arith"] == full["decoder_head_arith"] == "bf16x9-exact"
+    assert full["roofline"]["launches_timed"] == 5
+    assert full["roofline_hbm"] and all(h["launch_us"] > 0 for h in full["roofline_hbm"])

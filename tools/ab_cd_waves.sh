@@ -8,7 +8,7 @@ for r in 1 2 3; do
   done
 done
 run() {
-  python bench.py --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
+  python bench.py --full --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  ms/step', round(d['ms_per_step'],4), 'median', round(d['step_ms_median'],4), 'head us', round(d['roofline']['launch_us'],1), 'rest', round(d['ms_per_step']*1e3-d['roofline']['launch_us'],1))"
 }

@@ -9,7 +9,7 @@ for r in 1 2 3; do
   for l in $libs; do echo -n "$(basename $l)  "; env SCVAE_HIP_LIBRARY=$(pwd)/$l python tools/time_count_gemm.py; done
 done
 run() {
-  env SCVAE_HIP_LIBRARY=$1 python bench.py --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
+  env SCVAE_HIP_LIBRARY=$1 python bench.py --full --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  ms/step', round(d['ms_per_step'],4), 'median', round(d['step_ms_median'],4), 'head us', round(d['roofline']['launch_us'],1), 'rest', round(d['ms_per_step']*1e3-d['roofline']['launch_us'],1))"
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # A/B on one box: row groups of the producer / consumer head kernel (SCVAE_D4_ROW_GROUPS=1: off)
 run() {
-  python bench.py --no-other-workloads --no-cpu-baseline --steps 20 "$@" | python -c "
+  python bench.py --full --no-other-workloads --no-cpu-baseline --steps 20 "$@" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  ms/step', round(d['ms_per_step'],4), 'median', round(d['step_ms_median'],4), 'head us', round(d['roofline']['launch_us'],1), 'frac', round(d['roofline']['frac'],3))"
 }

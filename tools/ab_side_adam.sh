@@ -4,7 +4,7 @@
 # fetch does (SCVAE_SIDE_JOBS_AT), 4096-cell headline step: tools/ab_side_adam.sh
 cd "$(dirname "$0")/.."
 run() {
-  python bench.py --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
+  python bench.py --full --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  ms/step', round(d['ms_per_step'],4), 'median', round(d['step_ms_median'],4), 'head us', round(d['roofline']['launch_us'],1), 'rest', round(d['ms_per_step']*1e3-d['roofline']['launch_us'],1))"
 }

@@ -5,7 +5,7 @@
 # so that the next step's input layer finds the minibatch in the infinity cache; the heads' share
 # of Adam still forks).  tools/ab_side_jobs.sh [values...]   (default: 1 0)
 run() {
-  python bench.py --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
+  python bench.py --full --no-other-workloads --no-cpu-baseline --steps 300 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  ms/step', round(d['ms_per_step'],4), 'median', round(d['step_ms_median'],4), 'head us', round(d['roofline']['launch_us'],1), 'rest', round(d['ms_per_step']*1e3-d['roofline']['launch_us'],1))"
 }

@@ -11,7 +11,7 @@
 #   passes: FETCH_SIZE | WRITE_SIZE | SQ) for the same five training workloads.
 cd "$(dirname "$0")/.."
 P=${1:-r04e}; shift || true
-B="python bench.py --no-cpu-baseline --no-other-workloads $*"
+B="python bench.py --full --no-cpu-baseline --no-other-workloads $*"
 SQ="SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"
 run() {   # name, bench arguments
   local name=$1; shift
