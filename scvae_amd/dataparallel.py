@@ -57,6 +57,15 @@ def merge_batch_norm_statistics(gathered, counts):
     return mean, m2 / total
 
 
+def agreed_minimum(value, device="cpu"):
+    """The smallest of every rank's integer ``value``, on every rank: what each
+    rank sizes from its own free memory (the cells of an evaluation step) must
+    be one number before the ranks deal work by it."""
+    holder = torch.tensor([int(value)], dtype=torch.int64, device=device)
+    dist.all_reduce(holder, op=dist.ReduceOp.MIN)
+    return int(holder.item())
+
+
 # One gradient communicator per (backend, ranks) and process: ``dist.new_group`` is a collective
 # that allocates an RCCL communicator which is never freed, and ``model.train`` builds a new
 # synchroniser on every call.

@@ -401,6 +401,8 @@ class ModelBase:
                 noisy=noisy_preprocess
                 and validation_set.noisy_preprocess is not None)
             n_examples_valid = validation_set.number_of_examples
+        # (the epoch-end passes of every epoch step as the reserves below do)
+        self._decide_evaluation_step_cells(n_iw * n_mc, agree=world > 1)
         sync = None
         if world > 1:
             from scvae_amd.dataparallel import GradientSynchroniser
@@ -870,12 +872,24 @@ class ModelBase:
         F, L = self.feature_size, self.latent_size
         samples = 1 if deterministic_z else n_iw * n_mc
         # whole minibatches share a step where nothing but the averages is
-        # asked for (the epoch-end passes of train, a plain evaluate)
-        chunks = mu.evaluation_chunks(
-            n, minibatch_size,
-            0 if outputs else self._evaluation_step_cells(samples))
+        # asked for (the epoch-end passes of train, a plain evaluate), of the
+        # size train() / evaluate() decided where they reserved the workspace
+        step_cells = (None if outputs
+                      else self._decided_evaluation_step_cells(samples))
+        decided = step_cells is not None
+        if not decided and not outputs:   # (a pass of its own)
+            step_cells = self._evaluation_step_cells(samples)
+            if sync is not None:
+                from scvae_amd.dataparallel import agreed_minimum
+                step_cells = agreed_minimum(step_cells, device)
+        chunks = mu.evaluation_chunks(n, minibatch_size, step_cells or 0)
         starts = [start for start, _, _ in chunks]
         largest = max((cells for _, cells, _ in chunks), default=0)
+        if not decided:
+            engine.reserve(max(largest, 1), samples)
+        assert largest <= engine.max_cells, (
+            "an evaluation step of {} cells beyond the {} reserved".format(
+                largest, engine.max_cells))
         weights = torch.tensor([w for _, _, w in chunks], device=device)
         scalars = torch.zeros(len(starts), 8, device=device)
         kl_neurons = torch.zeros(len(starts), L, device=device)
@@ -915,6 +929,10 @@ class ModelBase:
         # product and run beside the hidden layers); two sets of buffers
         carried = (u16_buffer is not None and len(mine) > 1 and all(
             engine.accepts_counts_u16(cells, False) for _, _, cells in mine))
+        # (first row, cells, found there) of the minibatches the next step reads
+        # or fetches: resident rows count as filled once that step has been
+        # issued -- a step that raises leaves them to be fetched again
+        landed = []
         if carried:
             u16_sets = [u16_buffer, torch.empty_like(u16_buffer)
                         if resident is None else u16_buffer]
@@ -941,10 +959,7 @@ class ModelBase:
                 if not there:
                     request = x.request(all_rows[first:first + count],
                                         rows_out, constants_out)
-                    if resident is not None:
-                        resident[2][first:first + count] = True
-                else:
-                    self._evaluation_resident_hits += 1
+                landed.append((first, count, there))
                 noise = None
                 if not deterministic_z:
                     noise = self._noise_request(
@@ -978,11 +993,10 @@ class ModelBase:
                 if resident is not None:
                     dense, constants, filled = resident
                     xb, rc = dense[i:i + cells], constants[i:i + cells]
-                    if filled[i:i + cells].all():
-                        self._evaluation_resident_hits += 1
-                    else:
+                    there = bool(filled[i:i + cells].all())
+                    if not there:
                         x.gather_counts_u16(rows, out=xb, row_const_out=rc)
-                        filled[i:i + cells] = True
+                    landed.append((i, cells, there))
                     tb = xb
                 else:
                     xb = tb = x.gather_counts_u16(
@@ -1011,6 +1025,12 @@ class ModelBase:
                         outputs=out, scalars=scalars[j], decoder_extra=de,
                         count_sum=cs, x_counts=x.integer_counts,
                         next_minibatch=next_request, next_noise=next_noise)
+            for first, count, there in landed:
+                if there:
+                    self._evaluation_resident_hits += 1
+                elif resident is not None:
+                    resident[2][first:first + count] = True
+            landed.clear()
         # a step's means count once per minibatch it holds
         scalars *= weights[:, None]
         kl_neurons *= weights[:, None]
@@ -1086,10 +1106,35 @@ class ModelBase:
                 cells //= 2
         return cells
 
+    def _decide_evaluation_step_cells(self, samples, agree=False):
+        """Fix the cells per evaluation step of passes of ``samples`` samples
+        for one train() / evaluate(), where its workspace is reserved: sized
+        again at every pass, the step would follow the free memory of the
+        moment (a reserve() raises the budget, and a larger step re-binds a
+        workspace a GradientSynchroniser holds).  ``agree``: the smallest over
+        the ranks, which deal the steps by their index."""
+        cells = self._evaluation_step_cells(samples)
+        if agree:
+            from scvae_amd.dataparallel import agreed_minimum
+            cells = agreed_minimum(cells, self.engine.device)
+        self._evaluation_steps = {self._evaluation_step_key(samples): cells}
+        return cells
+
+    def _evaluation_step_key(self, samples):
+        return (int(samples), int(self.evaluation_chunk_cells),
+                int(self.evaluation_chunk_stacked_rows))
+
+    def _decided_evaluation_step_cells(self, samples):
+        """The decision of the running train() / evaluate(), or None."""
+        return getattr(self, "_evaluation_steps", {}).get(
+            self._evaluation_step_key(samples))
+
     def _evaluation_largest_step(self, n, minibatch_size, samples):
+        cells = self._decided_evaluation_step_cells(samples)
+        if cells is None:
+            cells = self._evaluation_step_cells(samples)
         return max((cells for _, cells, _ in mu.evaluation_chunks(
-            n, minibatch_size, self._evaluation_step_cells(samples))),
-            default=0)
+            n, minibatch_size, cells)), default=0)
 
     def _allocate_evaluation_outputs(self, n, n_batches, device):
         return {}
@@ -1243,6 +1288,11 @@ class ModelBase:
             n_iw = self.number_of_importance_samples["evaluation"]
             n_mc = self.number_of_monte_carlo_samples["evaluation"]
         sync = object() if world > 1 else None
+        if not outputs:   # (steps of several minibatches: decided here)
+            samples = 1 if use_deterministic_z else n_iw * n_mc
+            self._decide_evaluation_step_cells(samples, agree=world > 1)
+            engine.reserve(max(1, self._evaluation_largest_step(
+                n_examples_eval, minibatch_size, samples)), samples)
         evaluation = self._evaluation_pass(
             x_eval, t_eval, evaluation_set, minibatch_size, n_iw, n_mc,
             sync=sync, deterministic_z=use_deterministic_z, outputs=outputs)

@@ -142,3 +142,50 @@ def test_two_rank_step_equals_single_process():
     want = torch.cat([gW.reshape(-1), gb, gbeta, loss.reshape(1)])
     assert torch.allclose(grads, want, rtol=1e-10, atol=1e-12)
     assert torch.allclose(dmean, mean) and torch.allclose(dvar, var)
+
+
+def _minimum_worker(rank, world, port, values, out):
+    from scvae_amd.dataparallel import agreed_minimum
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    try:
+        dist.init_process_group("gloo", rank=rank, world_size=world,
+                                timeout=datetime.timedelta(seconds=60))
+    except Exception as error:   # the port was taken between pick and bind
+        out.put((RENDEZVOUS_FAILED, rank, repr(error)))
+        return
+    try:
+        out.put((rank, [agreed_minimum(v) for v in values[rank]]))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_agreed_minimum_is_the_smallest_on_every_rank():
+    """``agreed_minimum``: what ranks size from their own free memory (the
+    cells of an evaluation step) is one number -- the smallest -- on all of
+    them, whichever rank holds it; large values survive (int64)."""
+    values = [[4096, 1024, 1 << 40, 7], [2048, 4096, (1 << 40) + 1, 7]]
+    want = [2048, 1024, 1 << 40, 7]
+    ctx = mp.get_context("spawn")
+    results = None
+    for attempt in range(3):   # (only a rendezvous failure is retried)
+        out = ctx.Queue()
+        port = _free_port()
+        procs = [ctx.Process(target=_minimum_worker,
+                             args=(r, 2, port, values, out)) for r in range(2)]
+        for p in procs:
+            p.start()
+        results = [out.get(timeout=180) for _ in range(2)]
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.terminate()
+                p.join()
+                raise AssertionError("a rank did not exit")
+        if any(r[0] == RENDEZVOUS_FAILED for r in results):
+            results = None
+            continue
+        assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+        break
+    assert results is not None, "the gloo rendezvous failed three times"
+    assert sorted(results) == [(0, want), (1, want)]
