@@ -218,8 +218,14 @@ int32_t scvae_plan_uses_tile_chain(const scvae_plan* plan, int64_t cells, int32_
  * dropout / decoder extras, single process): the hidden layers, posterior heads and latent stage
  * of a step run as TWO cooperative launches (forwards, backwards: sixteen workgroups with a grid
  * barrier per layer, instead of ~27 launches; midchain.hip).
- * Default on; 0 keeps the chain of launches (the two are compared in tests/test_gpu_vae_step.py) */
+ * Default on; 0 keeps the chain of launches (the two are compared in tests/test_gpu_vae_step.py).
+ * scvae_plan_uses_mid_chain: whether a step of `cells` cells x `samples` samples (`training`: a
+ * training step, else an evaluation step) of this plan, as configured now, takes that path --
+ * including the run-time check that the sixteen workgroups can be co-resident on the current
+ * device (0 without one); always 0 for GMVAE plans, which have no mid chain. */
 int scvae_plan_set_mid_chain(scvae_plan* plan, int32_t enabled);
+int32_t scvae_plan_uses_mid_chain(const scvae_plan* plan, int64_t cells, int32_t samples,
+                                  int32_t training);
 
 /* One graph execution = session.run(...) in the reference loops
  * (train step va:1026-1029 / gm:1094-1097; evaluation va:1124-1135, 1983-2014).

@@ -1797,6 +1797,12 @@ int scvae_plan_set_mid_chain(scvae_plan* p, int32_t enabled) {
   p->use_mid_chain = enabled ? 1 : 0;
   return 0;
 }
+int32_t scvae_plan_uses_mid_chain(const scvae_plan* p, int64_t cells, int32_t samples,
+                                  int32_t training) {
+  if (!p || cells <= 0 || samples <= 0) return 0;
+  if (p->cfg.model_type != SCVAE_MODEL_VAE) return 0;   // (gmvae_step has no mid chain)
+  return mid_chain_ok(p, (int)cells, samples, training != 0) ? 1 : 0;
+}
 
 int scvae_plan_set_bn_one_launch(scvae_plan* p, int32_t enabled) {
   SCVAE_ARG(p && enabled >= 0 && enabled <= 2);

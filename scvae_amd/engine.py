@@ -378,6 +378,14 @@ class Engine:
         _lib.check(self.lib.scvae_plan_set_mid_chain(
             self.handle, 1 if enabled else 0), "scvae_plan_set_mid_chain")
 
+    def uses_mid_chain(self, cells, samples=1, training=True):
+        """Whether a step of ``cells`` x ``samples`` rows runs its hidden
+        layers, posterior heads and latent stage on the two cooperative
+        launches of the mid chain (VAE only; needs a GPU that holds their
+        sixteen workgroups at once)."""
+        return bool(self.lib.scvae_plan_uses_mid_chain(
+            self.handle, int(cells), int(samples), 1 if training else 0))
+
     def uses_tile_chain(self, cells, samples=1):
         """Whether a training step of ``cells`` x ``samples`` rows runs its
         hidden layers on the tile chain (one launch per layer and direction)."""

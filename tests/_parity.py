@@ -52,3 +52,29 @@ def close_maxnorm(got, want, rtol, what=""):
     err = np.abs(got - want).max() / scale if want.size else 0.0
     assert err <= rtol, "{}: max err {:.3e} of scale {:.3e}".format(
         what, err, scale)
+
+
+def close_per_tensor(got, want, table, rtol, atol=1e-9, what=""):
+    """``got``, ``want``: flat state buffers (``Engine.grads`` / ``.moving`` /
+    ``.params``) laid out by ``table`` (``Engine.param_table`` /
+    ``moving_table``: name -> (offset, shape)).  Every named tensor within
+    ``rtol`` of its OWN largest magnitude + ``atol``: the bound of a flat
+    comparison ``rtol * max|want| + atol``, but a small tensor (a bias, a beta,
+    a narrow layer's moving variance) is no longer measured against the
+    largest element of the whole buffer."""
+    got, want = _arrays(got, want)
+    got, want = got.reshape(-1), want.reshape(-1)
+    assert got.shape == want.shape, what
+    for name, (offset, shape) in table.items():
+        n = int(np.prod(shape))
+        a, b = got[offset:offset + n], want[offset:offset + n]
+        err = np.abs(a - b).max() if n else 0.0
+        scale = np.abs(b).max() if n else 0.0
+        assert err <= rtol * scale + atol, (
+            "{} {}: max err {:.3e} > {:.1e} x scale {:.3e} + {:.1e}".format(
+                what, name, err, rtol, scale, atol))
+
+
+def scalar_table(n):
+    """A ``close_per_tensor`` table of ``n`` separate scalars."""
+    return {"scalar {}".format(i): (i, (1,)) for i in range(n)}

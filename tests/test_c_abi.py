@@ -101,6 +101,41 @@ def test_bad_arguments_are_reported_not_crashed():
                           None, 0, None) == -1
 
 
+def test_path_queries_are_exported_and_answer_without_a_step():
+    """``scvae_plan_uses_mid_chain`` / ``_uses_tile_chain`` are bound and
+    answer on an unbound plan: a GMVAE plan never takes the mid chain, nor
+    does a NULL plan or an empty step; an unbound plan has no tile-chain
+    scratch yet."""
+    from scvae_amd import _lib
+    lib = _lib.load()
+    for name in ("scvae_plan_uses_mid_chain", "scvae_plan_uses_tile_chain"):
+        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
+    assert _lib.SIGNATURES["scvae_plan_uses_mid_chain"][1] == [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
+    assert lib.scvae_plan_uses_mid_chain(None, 100, 1, 1) == 0
+    for model_type in (_lib.MODEL_VAE, _lib.MODEL_GMVAE):
+        cfg = _lib.ModelConfig()
+        cfg.model_type = model_type
+        cfg.feature_size, cfg.latent_size, cfg.n_hidden = 30, 4, 1
+        cfg.hidden[0] = 16
+        cfg.likelihood = _lib.LIKELIHOOD_KINDS["poisson"][0]
+        cfg.batch_norm = 1
+        cfg.n_clusters = 3 if model_type == _lib.MODEL_GMVAE else 1
+        handle = ctypes.c_void_p()
+        assert lib.scvae_plan_create(ctypes.byref(cfg),
+                                     ctypes.byref(handle)) == 0
+        try:
+            assert lib.scvae_plan_uses_mid_chain(handle, 0, 1, 1) == 0
+            assert lib.scvae_plan_uses_mid_chain(handle, 16, 0, 1) == 0
+            if model_type == _lib.MODEL_GMVAE:
+                for training in (0, 1):
+                    assert lib.scvae_plan_uses_mid_chain(
+                        handle, 16, 1, training) == 0
+            assert lib.scvae_plan_uses_tile_chain(handle, 4096, 1) == 0
+        finally:
+            lib.scvae_plan_destroy(handle)
+
+
 def test_engine_refuses_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -3,10 +3,14 @@ the step must give the same result with and without the collectives installed
 (merge over one rank is the identity), for the VAE and the GMVAE."""
 import os
 
+import json
+
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
+
+from _parity import close_per_tensor, scalar_table
 
 pytestmark = pytest.mark.gpu
 
@@ -69,6 +73,12 @@ def test_step_with_sync_hook_equals_plain_step(cuda_device, single_rank_group,
     for a, b in zip(results[0], results[1]):
         scale = b.abs().max().item()
         assert (a - b).abs().max().item() <= 1e-5 * scale + 1e-9
+    # the same bound per scalar, per gradient and per moving statistic
+    tables = (scalar_table(results[0][0].numel()), eng.param_table,
+              eng.moving_table)
+    for what, a, b, table in zip(("scalars", "grad", "moving"), results[0],
+                                 results[1], tables):
+        close_per_tensor(a, b, table, rtol=1e-5, what=what)
 
 
 def _two_rank_worker(rank, port, model_type, result_path):
@@ -165,8 +175,21 @@ def _two_rank_worker(rank, port, model_type, result_path):
                 scale = b.abs().max().item()
                 worst = max(worst, (a - b).abs().max().item()
                             / (scale + 1e-12))
+            # and per scalar, gradient and moving statistic: [err, own scale]
+            tensors = {}
+            for kind, a, b, table in (
+                    ("scalar", scalars, ref_scalars,
+                     scalar_table(scalars.numel())),
+                    ("grad", eng.grads, ref.grads, eng.param_table),
+                    ("moving", eng.moving, ref.moving, eng.moving_table)):
+                for name, (offset, shape) in table.items():
+                    n = int(np.prod(shape))
+                    u = a[offset:offset + n].double()
+                    v = b[offset:offset + n].double()
+                    tensors[kind + " " + name] = [
+                        (u - v).abs().max().item(), v.abs().max().item()]
             with open(result_path, "w") as handle:
-                handle.write(repr(worst))
+                json.dump({"worst": worst, "tensors": tensors}, handle)
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -186,9 +209,18 @@ def test_two_ranks_equal_single_process(cuda_device, tmp_path, model_type):
     port = 29600 + (os.getpid() % 200) + CASES.index(model_type)
     mp.spawn(_two_rank_worker, args=(port, model_type, str(result)),
              nprocs=2, join=True)
-    worst = float(result.read_text())
-    assert worst <= (2e-5 if model_type in ("VAE", "GMVAE", "VAE-large",
-                                            "GMVAE-large") else 1e-4), worst
+    result = json.loads(result.read_text())
+    worst = result["worst"]
+    bound = (2e-5 if model_type in ("VAE", "GMVAE", "VAE-large",
+                                    "GMVAE-large") else 1e-4)
+    assert worst <= bound, worst
+    # the same bound per tensor, relative to the tensor's own magnitude; q(y|x)
+    # (GMVAE "Y/..."): 4x, the ratio test_gpu_baseline_configs.py gives its
+    # gradients against fp64 -- d/dlogit_k takes differences of per-cluster
+    # log-likelihoods of order 1e2, whose summation order the sharding changes
+    for name, (err, scale) in result["tensors"].items():
+        factor = 4.0 if name.startswith("grad Y/") else 1.0
+        assert err <= factor * bound * scale + 1e-9, (name, err, scale)
 
 
 def _model_train_worker(rank, port, directory, result_path):

@@ -8,6 +8,7 @@ import torch
 
 from oracle import likelihoods as lk
 from oracle import models as om
+from _parity import close_per_tensor
 
 pytestmark = pytest.mark.gpu
 
@@ -214,6 +215,11 @@ def test_training_loop_on_the_uint16_minibatch(tmp_path, cuda_device):
     for a, b in zip(*results):
         scale = b.abs().max().item()
         assert (a - b).abs().max().item() <= 1e-5 * scale + 1e-9
+    # the same bound per parameter and per moving statistic
+    for what, i, table in (("params", 0, model.engine.param_table),
+                           ("moving", 1, model.engine.moving_table)):
+        close_per_tensor(results[0][i], results[1][i], table, rtol=1e-5,
+                         what=what)
 
 
 def test_cli_train_and_evaluate(tmp_path, cuda_device, capsys):

@@ -61,3 +61,11 @@ def test_tile_chain_over_random_shapes(cuda_device):
     chain of launches, and bitwise repeatable."""
     out = _sweep("fuzz_tilechain.py", 0, 20)
     assert re.search(r"20 configurations, 0 failures", out), out[-3000:]
+
+
+def test_mid_chain_over_random_shapes(cuda_device):
+    """40 random small-minibatch configurations (rows x samples <= 128, widths
+    and latent size <= 128, 1-3 layers, every count likelihood): midchain.hip
+    against the chain of launches, per scalar and per named tensor."""
+    out = _sweep("fuzz_midchain.py", 0, 40)
+    assert re.search(r"^configs 40 bad 0$", out, re.M), out[-3000:]

@@ -10,7 +10,8 @@ import torch
 
 from oracle import models as om
 
-from _parity import LL_ATOL, LL_RTOL, close_elementwise
+from _parity import (LL_ATOL, LL_RTOL, close_elementwise, close_per_tensor,
+                     scalar_table)
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-4
@@ -293,6 +294,12 @@ def test_one_launch_batch_norm_matches_the_chunked_kernels(cuda_device, B, H):
     for a, b in zip(*results):
         scale = b.abs().max().item()
         assert (a - b).abs().max().item() <= 2e-5 * scale + 1e-9
+    # the same bound per scalar, per gradient and per moving statistic
+    tables = (scalar_table(results[0][0].numel()), eng.param_table,
+              eng.moving_table)
+    for what, a, b, table in zip(("scalars", "grad", "moving"), *results,
+                                 tables):
+        close_per_tensor(a, b, table, rtol=2e-5, what=what)
 
 
 @pytest.mark.parametrize("B,H,L,n_iw", [(100, (100, 100), 25, 1),
@@ -322,6 +329,10 @@ def test_mid_chain_matches_the_launch_chain(cuda_device, B, H, L, n_iw):
             if not name.endswith("weights"):
                 p.copy_(torch.randn(p.shape, generator=g) * 0.1)
         eng.set_mid_chain(mid)
+        eng.reserve(B, n_iw)
+        assert eng.uses_mid_chain(B, n_iw) == mid
+        assert eng.uses_mid_chain(B, n_iw, training=False) == mid
+        assert eng.uses_mid_chain(B, 1, training=False) == mid
         ll = torch.zeros(n_iw * B, device=cuda_device)
         qz = torch.zeros(B, L, device=cuda_device)
         klz = torch.zeros(L, device=cuda_device)
@@ -354,6 +365,12 @@ def test_mid_chain_matches_the_launch_chain(cuda_device, B, H, L, n_iw):
     for a, b in zip(*results):
         scale = b.abs().max().item()
         assert (a - b).abs().max().item() <= 2e-5 * scale + 1e-9
+    # the same bound per scalar, per gradient and per moving statistic
+    scalars = scalar_table(results[0][0].numel())
+    for i, table in ((0, scalars), (4, eng.param_table),
+                     (5, eng.moving_table), (6, scalars), (8, scalars)):
+        close_per_tensor(results[0][i], results[1][i], table, rtol=2e-5,
+                         what="output {}".format(i))
 
 
 @pytest.mark.parametrize("B,H,L,n_iw,n_mc", [(4096, (100, 100), 25, 1, 1),
@@ -445,6 +462,8 @@ def test_tile_chain_matches_the_launch_chain(cuda_device, B, H, L, n_iw, n_mc):
         for name, m in eng.named_moving_statistics().items():
             m.copy_(torch.rand(m.shape, generator=g) + 0.5)
         eng.set_tile_chain(tile)
+        eng.reserve(B, S)
+        assert eng.uses_tile_chain(B, S) == tile
         ll = torch.zeros(S * B, device=cuda_device)
         qz = torch.zeros(B, L, device=cuda_device)
         klz = torch.zeros(L, device=cuda_device)
@@ -470,3 +489,8 @@ def test_tile_chain_matches_the_launch_chain(cuda_device, B, H, L, n_iw, n_mc):
         scale = b.abs().max().item()
         assert (a - b).abs().max().item() <= 2e-5 * scale + 1e-9, (
             name, (a - b).abs().max().item(), scale)
+    # the same bound per scalar, per gradient and per moving statistic
+    for i, table in ((0, scalar_table(results[0][0].numel())),
+                     (4, eng.param_table), (5, eng.moving_table)):
+        close_per_tensor(results[0][i], results[1][i], table, rtol=2e-5,
+                         what=names[i])
