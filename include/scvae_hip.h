@@ -373,6 +373,15 @@ typedef struct scvae_step_args {
   const scvae_count_tiles* count_tiles;
   /* optional: optimiser update of this step / fetch and noise of the next one (see above) */
   const scvae_side_work* side;
+  /* Optional, only with counts_u16 (device, [cells]): counts_u16 is then the base of a RESIDENT
+   * matrix of pitch counts_ld -- e.g. a whole training set, densified once -- and row m of this
+   * step's minibatch is counts_u16 + counts_rows[m] * counts_ld (64-bit offsets; rows may repeat
+   * and come in any order).  The kernels that stream the minibatch read through the index: no
+   * dense copy of the minibatch is made, and the step is bit-identical to the one given those
+   * rows gathered.  row_const stays [cells] in minibatch order (scvae_gather_rows).  Only where
+   * scvae_plan_accepts_counts_rows says so, and not together with count_tiles; anything else is
+   * refused with an error.  NULL: counts_u16 is the minibatch itself. */
+  const int64_t* counts_rows;
 } scvae_step_args;
 /* Debugging aid: with SCVAE_WS_GUARD=1 in the environment (read once per process) every buffer
  * carved out of a plan's workspace is followed by a guard region (scvae_plan_workspace_bytes
@@ -389,6 +398,13 @@ int scvae_plan_step(scvae_plan* plan, const scvae_step_args* args, void* stream)
  * the layer that sees x at most 128 units wide, the count kernels enabled, and a minibatch large
  * enough for them to pay (the threshold of scvae_plan_set_count_gemm).  0 otherwise. */
 int scvae_plan_accepts_counts_u16(const scvae_plan* plan, int64_t cells, int32_t training);
+/* 1 if such a step can also read its minibatch through scvae_step_args.counts_rows (arguments as
+ * above): every kernel that reads the minibatch in that step takes the index directly -- VAE
+ * plans on the bf16x9 head arithmetic, the four count likelihoods, one likelihood pass per step
+ * (evaluation steps; training steps with training == 2), no head dropout.  Never 1 where
+ * scvae_plan_accepts_counts_u16 is 0.  0: gather the rows into an ordinary uint16 minibatch
+ * (scvae_gather_rows_u16) and call the step without an index. */
+int32_t scvae_plan_accepts_counts_rows(const scvae_plan* plan, int64_t cells, int32_t training);
 /* Decoder only, is_training = False: p_x_mean[rows, F] = mean of p(x|z) for given latent values
  * z[rows, L] -- `session.run(self.p_x_mean, feed_dict={self.z: z, self.is_training: False})`
  * in model.sample() (va:1680-1715; gm:2055-2079, where the one-hot y selects the fed z).
@@ -551,6 +567,17 @@ int scvae_count_gemm_tiles(int32_t mode, const scvae_count_tiles* tiles, const u
                            int64_t ld_other, int64_t N, const float* bias, int32_t relu, float* C,
                            int64_t ldc, void* workspace, int64_t workspace_bytes, void* stream);
 int scvae_gather_rows(const float* src, const int64_t* rows, int64_t n, float* out, void* stream);
+/* out[i, 0 .. cols) = src[rows[i], 0 .. cols), i < n: minibatch rows copied out of a resident
+ * uint16 matrix (row pitches ld_src, ld_out >= cols, in elements; 64-bit row offsets; rows may
+ * repeat, any order).  16-byte loads and stores where both bases are 16-byte aligned and both
+ * pitches multiples of 8, element by element otherwise.  Columns of out beyond cols are left as
+ * they are: pass cols = the pitch to copy the zero padding of scvae_csr_densify_u16 rows too. */
+int scvae_gather_rows_u16(const uint16_t* src, int64_t ld_src, const int64_t* rows, int64_t n,
+                          int64_t cols, uint16_t* out, int64_t ld_out, void* stream);
+/* the same rows as fp32 (counts convert exactly): the minibatch of a step that takes no uint16
+ * batch (scvae_plan_accepts_counts_u16 == 0), out of the same resident matrix */
+int scvae_gather_rows_u16_f32(const uint16_t* src, int64_t ld_src, const int64_t* rows, int64_t n,
+                              int64_t cols, float* out, int64_t ld_out, void* stream);
 /* ---- the small ops of the graph, stand-alone (the kernels scvae_plan_step launches; SURVEY.md
  *      section 8b).  Row-major contiguous fp32 unless a pitch is given. ---- */
 /* tf.contrib.layers.batch_norm(center=True, scale=False, is_training=True) inside dense_layer

@@ -87,6 +87,7 @@ class StepArgs(Structure):
         ("counts_ld", c_int64),
         ("count_tiles", c_void_p),
         ("side", c_void_p),
+        ("counts_rows", c_void_p),
     ]
 
 
@@ -183,6 +184,13 @@ SIGNATURES = {
         c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
         c_void_p]),
     "scvae_plan_accepts_counts_u16": (c_int32, [c_void_p, c_int64, c_int32]),
+    "scvae_plan_accepts_counts_rows": (c_int32, [c_void_p, c_int64, c_int32]),
+    "scvae_gather_rows_u16": (c_int32, [
+        c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+        c_void_p]),
+    "scvae_gather_rows_u16_f32": (c_int32, [
+        c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+        c_void_p]),
     "scvae_count_gemm_u16": (c_int32, [
         c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64,
         c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,

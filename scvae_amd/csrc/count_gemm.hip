@@ -129,221 +129,27 @@ constexpr int CD_ROW = 48;            // LDS bytes per (term, column) row: 32 + 
 
 // NW: waves per workgroup -- 4 (256 genes, two workgroups per CU) or 8 (512 genes, one per CU: the
 // dA planes of a chunk are fetched and parked once for twice the genes)
+//
+// IDX (count_gemm_dw_rows_kernel): X is a resident matrix and cell k of the contraction is its row
+// xrows[k].  A chunk's 16 indices are wave-uniform -- two scalar loads of eight -- and a load
+// instruction, which covers cells kc + j (lanes 0 .. 31) and kc + j + 8 (lanes 32 .. 63), takes
+// its row base from a per-lane select between two scalar offsets: no vector load is added.
 template <int NT, typename XT, bool PAIR = false, bool USE_STEADY = false, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void count_gemm_dw_kernel(
     const XT* __restrict__ X, int ldx, int M, int K, const uint16_t* __restrict__ T, int Kpad,
     int N, int k_chunk, float* __restrict__ out, int ldo) {
-  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][3 * CG_NP * CD_ROW];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, kg = lane >> 5;
-  constexpr int NTHR = 64 * NW, NPC = (768 + NTHR - 1) / NTHR;   // pieces of dA per thread
-  const int m_w = blockIdx.x * (NW * CG_TM) + w * CG_TM;       // first gene of this wave
-  const int k_begin = blockIdx.y * k_chunk;
-  const int k_end = min(K, k_begin + k_chunk);
-
-  f32x16 acc[2][NT];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[t][q][i] = 0.f;
-
-  // raw[slot][t][j]  <->  cell kc + 8 kg + j of gene tile t; uniform row pointer + per-lane
-  // 32-bit element offset (gene + 8 kg rows)
-  // PAIR (uint16 counts, M even): a lane reads genes 2 li and 2 li + 1 of the wave's 64 with one
-  // 4-byte load -- gene tile 0 takes the even genes, tile 1 the odd ones -- half the load
-  // instructions of the lane-per-gene pattern for the same bytes.
-  static_assert(!PAIR || sizeof(XT) == 2, "gene pairs: uint16 counts");
-  XT raw[2][2][PAIR ? 1 : 8];
-  unsigned rawp[2][PAIR ? 8 : 1];
-  unsigned xoff[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-    xoff[t] = (unsigned)(8 * kg) * (unsigned)ldx +
-              (PAIR ? (unsigned)min(m_w + 2 * li, M - 2)
-                    : (unsigned)min(m_w + 32 * t + li, M - 1));
-  // the count of gene tile t, cell j of the slot, as fp32
-  auto value = [&](auto slot_tag, int t, int j) -> float {
-    constexpr int SLOT = decltype(slot_tag)::value;
-    if constexpr (PAIR) return (float)(t == 0 ? (rawp[SLOT][j] & 0xFFFFu) : (rawp[SLOT][j] >> 16));
-    else return count_to_f32(raw[SLOT][t][j]);
-  };
-  u32x4 breg[USE_STEADY ? 2 : 1][NPC];
-  auto load_x = [&](int kc, auto slot_tag) {
-    constexpr int SLOT = decltype(slot_tag)::value;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const XT* srow = X + (size_t)(kc + j) * ldx;               // uniform: scalar base
-      if constexpr (PAIR) {
-        rawp[SLOT][j] = cg_load<(SCVAE_CG_NT & 2) != 0>(
-            reinterpret_cast<const unsigned*>(srow + xoff[0]));
-      } else {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          raw[SLOT][t][j] = cg_load<(SCVAE_CG_NT & 2) != 0>(srow + xoff[t]);
-      }
-    }
-  };
-  auto load_b = [&](int kc, int slot = 0) {
-#pragma unroll
-    for (int i = 0; i < NPC; ++i) {
-      const int p = tid + NTHR * i;                // 768 pieces: (term, column, half)
-      const int row = p >> 1, part = p & 1;        // row = term * 128 + column
-      // (columns beyond N: the last live column's piece again -- a line this wave requests
-      //  anyway, no branch around the load; what they multiply into is never stored)
-      const int col = row & (CG_NP - 1), rowl = col < N ? row : row - col + (N - 1);
-      if (p < 768 && col < NT * 32)
-        breg[slot][i] = *reinterpret_cast<const u32x4*>(T + cg_piece<CD_BK>(kc, rowl, part));
-    }
-  };
-  auto store_b = [&](int buf, int slot = 0) {
-#pragma unroll
-    for (int i = 0; i < NPC; ++i) {
-      const int p = tid + NTHR * i;
-      const int row = p >> 1, part = p & 1;
-      if (p < 768 && (row & (CG_NP - 1)) < NT * 32)
-        *reinterpret_cast<u32x4*>(&Bs[buf][row * CD_ROW + part * 16]) = breg[slot][i];
-    }
-  };
-  // (USE_STEADY: every request of the loop is unconditional -- a chunk index beyond the split's
-  //  last chunk is clamped to it, its data never used -- so that the compiler can count the
-  //  loads in flight; dA travels TWO chunks ahead, like x)
-  const int k_last = k_end - CD_BK;
-  auto clampk = [&](int k) { return min(k, k_last); };
-
-  if (k_begin < k_end) {
-    load_x(k_begin, std::integral_constant<int, 0>{});
-    if (USE_STEADY) load_x(clampk(k_begin + CD_BK), std::integral_constant<int, 1>{});
-    else if (k_begin + CD_BK < k_end) load_x(k_begin + CD_BK, std::integral_constant<int, 1>{});
-    load_b(k_begin);
-    store_b(0);
-    if (USE_STEADY) load_b(clampk(k_begin + CD_BK), 1);
-  }
-  __syncthreads();
-
-  const int frag_off = li * CD_ROW + 16 * kg;
-  // STEADY (compile time): chunks j + 1 and j + 2 exist -- requests and hand-over unconditional
-  // (see count_gemm_fwd_kernel).  Measured on this kernel the unconditional loop is SLOWER (178 vs
-  // 155 us at 4096 x 32 738: both x chunks then really stay in flight, the kernel sits at 256
-  // VGPRs and the deeper queue does not pay), so USE_STEADY defaults to off here.
-  auto chunk = [&](int kc, auto buf_tag, auto steady_tag) {
-    constexpr int BUF = decltype(buf_tag)::value;        // LDS buffer and x slot of this chunk
-    constexpr bool STEADY = decltype(steady_tag)::value;
-    // ---- cut the counts of this chunk into hi / lo bf16 fragments ----
-    u32x4 ahi[2], alo[2];
-    unsigned low_bits = 0u;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      unsigned h[4];
-#pragma unroll
-      for (int pr = 0; pr < 4; ++pr) {
-        const unsigned u0 = __float_as_uint(value(buf_tag, t, 2 * pr));
-        const unsigned u1 = __float_as_uint(value(buf_tag, t, 2 * pr + 1));
-        low_bits |= u0 | u1;
-        h[pr] = __builtin_amdgcn_perm(u1, u0, 0x07060302u);          // upper halves
-      }
-      ahi[t] = u32x4{h[0], h[1], h[2], h[3]};
-    }
-    const bool need_lo =
-        __builtin_amdgcn_readfirstlane(__any((int)((low_bits & 0xFFFFu) != 0u)));
-    if (need_lo) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        unsigned l[4];
-#pragma unroll
-        for (int pr = 0; pr < 4; ++pr) {
-          const float x0 = value(buf_tag, t, 2 * pr);
-          const float x1 = value(buf_tag, t, 2 * pr + 1);
-          const float l0 = x0 - __uint_as_float(__float_as_uint(x0) & 0xFFFF0000u);
-          const float l1 = x1 - __uint_as_float(__float_as_uint(x1) & 0xFFFF0000u);
-          l[pr] = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
-        }
-        alo[t] = u32x4{l[0], l[1], l[2], l[3]};
-      }
-    }
-    // ---- requests: dA one chunk ahead, x two chunks ahead (the slot just converted).  dA first:
-    //      in the unconditional loop (STEADY) the wait for dA at the end of the chunk (store_b)
-    //      is then vmcnt(8) and leaves the eight younger x loads in flight across the barrier;
-    //      with x first it was vmcnt(0) -- the counter retires in issue order -- and in the
-    //      conditional loop it still is (the compiler cannot count loads under a branch): every
-    //      x request lands within the chunk that issued it.  Measured (round 5, SCVAE_CD_STEADY,
-    //      tools/ab_cd_steady.sh): with the x requests really in flight the kernel is SLOWER,
-    //      138.8-142.2 against 134.7-137.2 us stand-alone, + 7 us in the step -- as round 2
-    //      found with the other order; the default stays the conditional loop ----
-    const bool has_next = STEADY || kc + CD_BK < k_end;
-    if (STEADY) {
-      load_b(clampk(kc + 2 * CD_BK), BUF);
-      __builtin_amdgcn_sched_barrier(0);
-      load_x(clampk(kc + 2 * CD_BK), buf_tag);
-    } else {
-      if (has_next) load_b(kc + CD_BK);
-      __builtin_amdgcn_sched_barrier(0);
-      if (kc + 2 * CD_BK < k_end) load_x(kc + 2 * CD_BK, buf_tag);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-
-    const unsigned char* bcur = Bs[BUF] + frag_off;
-#pragma unroll
-    for (int term = 2; term >= 0; --term) {              // smallest term first
-      bf16x8 fr[NT];
-#pragma unroll
-      for (int q = 0; q < NT; ++q)
-        fr[q] = as_bf16x8(*reinterpret_cast<const u32x4*>(
-            bcur + (term * CG_NP + q * 32) * CD_ROW));
-      if (need_lo) {
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(alo[0]), fr[q], acc[0][q],
-                                                              0, 0, 0);
-          acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(alo[1]), fr[q], acc[1][q],
-                                                              0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < NT; ++q) {
-        acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ahi[0]), fr[q], acc[0][q], 0,
-                                                            0, 0);
-        acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ahi[1]), fr[q], acc[1][q], 0,
-                                                            0, 0);
-      }
-    }
-    if (STEADY) store_b(BUF ^ 1, BUF ^ 1);     // (dA of chunk kc + 1: requested a chunk ago)
-    else if (has_next) store_b(BUF ^ 1);
-    lds_barrier();       // (LDS only: the x requests stay in flight across it)
-  };
-  {
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-    int kc = k_begin;
-    if (USE_STEADY) {
-      for (; kc + CD_BK < k_end; kc += 2 * CD_BK) {     // pairs of chunks
-        chunk(kc, B0{}, std::true_type{});
-        chunk(kc + CD_BK, B1{}, std::true_type{});
-      }
-      if (kc < k_end) chunk(kc, B0{}, std::true_type{});   // an odd last one
-    } else
-    for (; kc < k_end; kc += 2 * CD_BK) {
-      chunk(kc, B0{}, std::false_type{});
-      if (kc + CD_BK < k_end) chunk(kc + CD_BK, B1{}, std::false_type{});
-    }
-  }
-
-  float* dst = out + (size_t)blockIdx.y * M * ldo;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int col = q * 32 + li;
-      if (col >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * kg;         // row of the gene tile
-        const int m = PAIR ? m_w + 2 * i + t : m_w + 32 * t + i;
-        if (m < M) dst[(size_t)m * ldo + col] = acc[t][q][r];
-      }
-    }
+  constexpr bool IDX = false;
+  const int64_t* const xrows = nullptr;
+#include "count_gemm_dw_body.inc"
+}
+template <int NT, bool PAIR, int NW>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void count_gemm_dw_rows_kernel(
+    const uint16_t* __restrict__ X, int ldx, int M, int K, const uint16_t* __restrict__ T,
+    int Kpad, int N, int k_chunk, float* __restrict__ out, int ldo,
+    const int64_t* __restrict__ xrows) {
+  using XT = uint16_t;
+  constexpr bool USE_STEADY = false, IDX = true;
+#include "count_gemm_dw_body.inc"
 }
 
 // ---- forward (MODE 0) with the x tile staged through LDS ----
@@ -363,233 +169,25 @@ static size_t cf_lds_bytes(int NQ) {
   return 4 * (size_t)CF_A_BYTES + 2 * (size_t)(3 * 64 * NQ * CG_ROW) + 2 * 8 * sizeof(int);
 }
 
+// IDX (count_gemm_fwd_rows_kernel): X is a resident matrix and cell m of the minibatch is its row
+// xrows[m]; a thread reads the indices of its PCS staging rows once, ahead of the main loop.
 template <int NQ, typename XT>
 __global__ __launch_bounds__(512) void count_gemm_fwd_kernel(
     const XT* __restrict__ X, int ldx, int M, int K, const uint16_t* __restrict__ T, int Kpad,
     int N, int k_chunk, float* __restrict__ out, int ldo, const float* __restrict__ bias,
     int act, int direct) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char cf_smem[];
-  constexpr int NCOL = 64 * NQ;                         // columns staged per term
-  constexpr int B_BYTES = 3 * NCOL * CG_ROW;
-  unsigned char* Ahi = cf_smem;                         // [2][256][80]
-  unsigned char* Alo = Ahi + 2 * CF_A_BYTES;            // [2][256][80]
-  unsigned char* Bsm = Alo + 2 * CF_A_BYTES;            // [2][3][NCOL][80]
-  int* lo_flag = reinterpret_cast<int*>(Bsm + 2 * B_BYTES);   // [2][8]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, kg = lane >> 5;
-  const int rg = w & 3, q0 = (w >> 2) * NQ;
-  const int m0 = blockIdx.x * CF_BM;
-  const int k_begin = blockIdx.y * k_chunk;
-  const int k_end = min(K, k_begin + k_chunk);
-
-  f32x16 acc[2][NQ];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[t][q][i] = 0.f;
-
-  // zero both lo planes once (a wave only ever rewrites its own rows)
-  for (int i = tid; i < 2 * CF_A_BYTES / 16; i += 512)
-    reinterpret_cast<u32x4*>(Alo)[i] = u32x4{0u, 0u, 0u, 0u};
-
-  // ---- staging: 16-byte pieces of the [256, 32] tile; fp32: 8 per row, thread -> 4 pieces (row
-  // (tid >> 3) + 64 i, floats 4 (tid & 7) .. + 3); uint16: 4 per row, thread -> 2 pieces (row
-  // (tid >> 2) + 128 i, counts 8 (tid & 3) .. + 7) ----
-  constexpr int EPP = 16 / (int)sizeof(XT);             // elements per piece
-  constexpr int PPR = CG_BK / EPP;                      // pieces per row
-  constexpr int RPP = 512 / PPR;                        // rows per pass
-  constexpr int PCS = CF_BM / RPP;                      // pieces per thread
-  const int part = tid & (PPR - 1);
-  const XT* xsrc[PCS];
-#pragma unroll
-  for (int i = 0; i < PCS; ++i) {
-    const int m = min(m0 + tid / PPR + RPP * i, M - 1);
-    xsrc[i] = X + (size_t)m * ldx + EPP * part;
-  }
-  const int a_off = (tid / PPR) * CG_ROW + part * (2 * EPP);   // + i * RPP rows
-  // two chunks of staging registers: chunk c + 2 is requested while chunk c is multiplied and
-  // chunk c + 1 (requested one iteration earlier) is converted and parked -- a full iteration
-  // plus the MFMA phase of latency tolerance with a single workgroup per CU
-  f32x4u raw[2][PCS];
-  u32x4 breg[2][3];
-  auto load_tiles = [&](int kc, int slot) {
-#pragma unroll
-    for (int i = 0; i < PCS; ++i) {
-      const f32x4u* src = reinterpret_cast<const f32x4u*>(xsrc[i] + kc);
-      if constexpr ((SCVAE_CG_NT & 1) != 0) raw[slot][i] = __builtin_nontemporal_load(src);
-      else raw[slot][i] = *src;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int p = tid + 512 * i;                      // (term, column, quarter)
-      const int row = p >> 2, prt = p & 3;              // row = term * 128 + column
-      // (columns beyond N: the last live column's piece again, as in count_gemm_dw_kernel)
-      const int col = row & (CG_NP - 1), rowl = col < N ? row : row - col + (N - 1);
-      if (col < NCOL)
-        breg[slot][i] = *reinterpret_cast<const u32x4*>(T + cg_piece<CG_BK>(kc, rowl, prt));
-    }
-  };
-  bool dirty0 = false, dirty1 = false;                  // this wave's lo rows of buffer b are set
-  auto store_tiles = [&](int buf, int slot) {
-    unsigned low = 0u;
-    // the piece's counts as fp32 bit patterns (uint16: two per loaded dword)
-    auto bits_of = [&](int i, unsigned* u) {
-      if constexpr (sizeof(XT) == 4) {
-        u[0] = __float_as_uint(raw[slot][i].x); u[1] = __float_as_uint(raw[slot][i].y);
-        u[2] = __float_as_uint(raw[slot][i].z); u[3] = __float_as_uint(raw[slot][i].w);
-      } else {
-        const unsigned w[4] = {__float_as_uint(raw[slot][i].x), __float_as_uint(raw[slot][i].y),
-                               __float_as_uint(raw[slot][i].z), __float_as_uint(raw[slot][i].w)};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          u[2 * j] = __float_as_uint((float)(w[j] & 0xFFFFu));
-          u[2 * j + 1] = __float_as_uint((float)(w[j] >> 16));
-        }
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < PCS; ++i) {
-      unsigned u[EPP], h[EPP / 2];
-      bits_of(i, u);
-#pragma unroll
-      for (int j = 0; j < EPP / 2; ++j) {
-        low |= u[2 * j] | u[2 * j + 1];
-        h[j] = __builtin_amdgcn_perm(u[2 * j + 1], u[2 * j], 0x07060302u);     // upper halves
-      }
-      unsigned char* dst = Ahi + buf * CF_A_BYTES + a_off + i * RPP * CG_ROW;
-      if constexpr (EPP == 4) *reinterpret_cast<uint2*>(dst) = uint2{h[0], h[1]};
-      else *reinterpret_cast<u32x4*>(dst) = u32x4{h[0], h[1], h[2], h[3]};
-    }
-    const bool need = __builtin_amdgcn_readfirstlane(__any((int)((low & 0xFFFFu) != 0u)));
-    if (need || (buf ? dirty1 : dirty0)) {
-#pragma unroll
-      for (int i = 0; i < PCS; ++i) {
-        unsigned u[EPP], l[EPP / 2];
-        bits_of(i, u);
-#pragma unroll
-        for (int j = 0; j < EPP / 2; ++j) {
-          const float l0 = __uint_as_float(u[2 * j]) - __uint_as_float(u[2 * j] & 0xFFFF0000u);
-          const float l1 = __uint_as_float(u[2 * j + 1]) - __uint_as_float(u[2 * j + 1] & 0xFFFF0000u);
-          l[j] = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
-        }
-        unsigned char* dst = Alo + buf * CF_A_BYTES + a_off + i * RPP * CG_ROW;
-        if constexpr (EPP == 4) *reinterpret_cast<uint2*>(dst) = uint2{l[0], l[1]};
-        else *reinterpret_cast<u32x4*>(dst) = u32x4{l[0], l[1], l[2], l[3]};
-      }
-    }
-    if (buf) dirty1 = need; else dirty0 = need;
-    if (lane == 0) lo_flag[buf * 8 + w] = need ? 1 : 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int p = tid + 512 * i;
-      const int row = p >> 2, prt = p & 3;
-      const int term = row >> 7, col = row & (CG_NP - 1);
-      if (col < NCOL)
-        *reinterpret_cast<u32x4*>(Bsm + buf * B_BYTES + (term * NCOL + col) * CG_ROW + prt * 16) =
-            breg[slot][i];
-    }
-  };
-
-  __syncthreads();                                      // lo planes zeroed
-  if (k_begin < k_end) {
-    load_tiles(k_begin, 0);
-    if (k_begin + CG_BK < k_end) load_tiles(k_begin + CG_BK, 1);
-    store_tiles(0, 0);
-  }
-  __syncthreads();
-
-  const int a_frag = (64 * rg + li) * CG_ROW + 32 * kg;      // + 32 rows * t, + 16 s
-  const int b_frag = (q0 * 32 + li) * CG_ROW + 32 * kg;      // + term * NCOL rows, + 32 rows * q
-  // one chunk; BUF (compile time: the staging registers are indexed statically) = LDS buffer and
-  // staging slot of chunk j = j & 1
-  // STEADY (compile time): chunks j + 1 and j + 2 exist, so the request and the hand-over are
-  // unconditional -- with conditions the compiler cannot pair them up and waits for every
-  // outstanding load at the loop header, which cancels the second chunk of latency tolerance
-  auto chunk = [&](int kc, auto buf_tag, auto steady_tag) {
-    constexpr int BUF = decltype(buf_tag)::value;
-    constexpr bool STEADY = decltype(steady_tag)::value;
-    // chunk j + 2 -> staging slot BUF (chunk j left it for LDS before this iteration)
-    if (STEADY || kc + 2 * CG_BK < k_end) load_tiles(kc + 2 * CG_BK, BUF);
-    __builtin_amdgcn_sched_barrier(0);
-
-    const bool need_lo =
-        __builtin_amdgcn_readfirstlane(__any(lo_flag[BUF * 8 + (lane & 7)]));
-    const unsigned char* ah = Ahi + BUF * CF_A_BYTES + a_frag;
-    const unsigned char* al = Alo + BUF * CF_A_BYTES + a_frag;
-    const unsigned char* bb = Bsm + BUF * B_BYTES + b_frag;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 fh[2], fl[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-        fh[t] = as_bf16x8(*reinterpret_cast<const u32x4*>(ah + t * 32 * CG_ROW + 16 * s));
-      if (need_lo) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          fl[t] = as_bf16x8(*reinterpret_cast<const u32x4*>(al + t * 32 * CG_ROW + 16 * s));
-      }
-#pragma unroll
-      for (int term = 2; term >= 0; --term) {           // smallest term first
-        bf16x8 fb[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          fb[q] = as_bf16x8(*reinterpret_cast<const u32x4*>(
-              bb + (term * NCOL + q * 32) * CG_ROW + 16 * s));
-        if (need_lo) {
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) {
-            acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[0], fb[q], acc[0][q], 0, 0, 0);
-            acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[1], fb[q], acc[1][q], 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[0], fb[q], acc[0][q], 0, 0, 0);
-          acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[1], fb[q], acc[1][q], 0, 0, 0);
-        }
-      }
-    }
-    // chunk j + 1 (requested one iteration ago, staging slot BUF ^ 1) -> LDS buffer BUF ^ 1
-    // (scheduling fence: the conversion and its wait for the loads stay below the MFMAs)
-    __builtin_amdgcn_sched_barrier(0);
-    if (STEADY || kc + CG_BK < k_end) store_tiles(BUF ^ 1, BUF ^ 1);
-    lds_barrier();       // (LDS only: the requests for chunk j + 2 stay in flight across it)
-  };
-  {
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-    int kc = k_begin;
-    for (; kc + 3 * CG_BK < k_end; kc += 2 * CG_BK) {   // chunks j, j + 1 with j + 3 in range
-      chunk(kc, B0{}, std::true_type{});
-      chunk(kc + CG_BK, B1{}, std::true_type{});
-    }
-    for (; kc < k_end; kc += 2 * CG_BK) {               // the last one to three chunks
-      chunk(kc, B0{}, std::false_type{});
-      if (kc + CG_BK < k_end) chunk(kc + CG_BK, B1{}, std::false_type{});
-    }
-  }
-
-  float* dst = direct ? out : out + (size_t)blockIdx.y * M * ldo;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int col = (q0 + q) * 32 + li;
-      if (col >= N) continue;
-      const float bv = (direct && bias != nullptr) ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + 64 * rg + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * kg;
-        if (m < M) {
-          float v = acc[t][q][r] + bv;
-          if (direct && act == ACT_RELU) v = fmaxf(v, 0.f);
-          dst[(size_t)m * ldo + col] = v;
-        }
-      }
-    }
+  constexpr bool IDX = false;
+  const int64_t* const xrows = nullptr;
+#include "count_gemm_fwd_body.inc"
+}
+template <int NQ>
+__global__ __launch_bounds__(512) void count_gemm_fwd_rows_kernel(
+    const uint16_t* __restrict__ X, int ldx, int M, int K, const uint16_t* __restrict__ T,
+    int Kpad, int N, int k_chunk, float* __restrict__ out, int ldo,
+    const float* __restrict__ bias, int act, int direct, const int64_t* __restrict__ xrows) {
+  using XT = uint16_t;
+  constexpr bool IDX = true;
+#include "count_gemm_fwd_body.inc"
 }
 
 // fixed-order sum of the split-K slabs, + the K % 32 leftover terms of the contraction (plain
@@ -599,28 +197,18 @@ __global__ __launch_bounds__(256) void count_gemm_reduce_kernel(
     const float* __restrict__ slabs, const float* __restrict__ bias, float* __restrict__ C, int M,
     int N, int ldc, int splits, int act, int mode, const XT* __restrict__ X, int ldx,
     const float* __restrict__ other, int ld_other, int k_main, int K) {
-  const size_t total = (size_t)M * N;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const int row = (int)(i / N), col = (int)(i % N);
-    float s = 0.f;
-    int z = 0;
-    for (; z + 8 <= splits; z += 8) {      // (eight slabs' loads in flight, summed in slab order)
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = slabs[(size_t)(z + u) * total + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; z < splits; ++z) s += slabs[(size_t)z * total + i];
-    for (int k = k_main; k < K; ++k) {
-      const float xv = count_to_f32(mode == 0 ? X[(size_t)row * ldx + k] : X[(size_t)k * ldx + row]);
-      s = fmaf(xv, other[(size_t)k * ld_other + col], s);
-    }
-    if (bias) s += bias[col];
-    if (act == ACT_RELU) s = fmaxf(s, 0.f);
-    C[(size_t)row * ldc + col] = s;
-  }
+  constexpr bool IDX = false;
+  const int64_t* const xrows = nullptr;
+#include "count_gemm_reduce_body.inc"
+}
+__global__ __launch_bounds__(256) void count_gemm_reduce_rows_kernel(
+    const float* __restrict__ slabs, const float* __restrict__ bias, float* __restrict__ C, int M,
+    int N, int ldc, int splits, int act, int mode, const uint16_t* __restrict__ X, int ldx,
+    const float* __restrict__ other, int ld_other, int k_main, int K,
+    const int64_t* __restrict__ xrows) {
+  using XT = uint16_t;
+  constexpr bool IDX = true;
+#include "count_gemm_reduce_body.inc"
 }
 
 // (A/B: SCVAE_CD_STEADY=0 / 1 -- the weight-gradient kernel's unconditional main loop)
@@ -690,8 +278,10 @@ static bool cf_two_roles() {
 template <typename XT>
 static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, int rows, int cols,
                            const float* other, int ld_other, int N, const float* bias, int act,
-                           float* C, int ldc, void* workspace, size_t workspace_bytes) {
+                           float* C, int ldc, void* workspace, size_t workspace_bytes,
+                           const int64_t* xrows = nullptr) {
   SCVAE_ARG(x && other && C && workspace);
+  SCVAE_ARG(!xrows || sizeof(XT) == 2);        // (a row index: the resident uint16 matrix)
   SCVAE_ARG(mode == 0 || mode == 1);
   SCVAE_ARG(count_gemm_supported(N) && ld_other >= N && ldc >= N && ldx >= cols);
   // 16-byte loads of a row need 4-byte aligned rows
@@ -746,9 +336,21 @@ static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, i
                        (const uint32_t*)nullptr, 0, 0, reinterpret_cast<const uint16_t*>(x), ldx, \
                        M, k_main, T, Kpad, N, k_chunk, dst, ldo, kbias, kact, kdirect);           \
   } while (0)
-      if (sizeof(XT) == 2 && cf_two_roles()) {
+      // (x through a row index: always count_gemm_fwd_kernel's indexed form; uint16 only, above)
+      const uint16_t* x16 = xrows ? reinterpret_cast<const uint16_t*>(x) : nullptr;
+#define SCVAE_CFR(NQ_)                                                                            \
+  do {                                                                                            \
+    auto kfn = count_gemm_fwd_rows_kernel<NQ_>;                                                   \
+    SCVAE_HIP(max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)lds));                     \
+    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, stream, x16, ldx, M, k_main, T, Kpad, N, k_chunk, \
+                       dst, ldo, kbias, kact, kdirect, xrows);                                    \
+  } while (0)
+      if (xrows) {
+        if (NQ == 2) SCVAE_CFR(2); else SCVAE_CFR(1);
+      } else if (sizeof(XT) == 2 && cf_two_roles()) {
         if (NQ == 2) SCVAE_CF2(2); else SCVAE_CF2(1);
       } else if (NQ == 2) SCVAE_CF(2); else SCVAE_CF(1);
+#undef SCVAE_CFR
 #undef SCVAE_CF2
 #undef SCVAE_CF
     } else {
@@ -757,6 +359,18 @@ static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, i
 #define SCVAE_CD(NT_)                                                                             \
   do {                                                                                            \
     if constexpr (sizeof(XT) == 2) {                                                              \
+      if (xrows) {          /* x through a row index: the same geometries, indexed */             \
+        if ((M & 1) != 0)                                                                         \
+          hipLaunchKernelGGL((count_gemm_dw_rows_kernel<NT_, false, 4>), grid, dim3(256), 0,      \
+                             stream, x, ldx, M, k_main, T, Kpad, N, k_chunk, dst, ldo, xrows);    \
+        else if (nw == 8)                                                                         \
+          hipLaunchKernelGGL((count_gemm_dw_rows_kernel<NT_, true, 8>), grid, dim3(512), 0,       \
+                             stream, x, ldx, M, k_main, T, Kpad, N, k_chunk, dst, ldo, xrows);    \
+        else                                                                                      \
+          hipLaunchKernelGGL((count_gemm_dw_rows_kernel<NT_, true, 4>), grid, dim3(256), 0,       \
+                             stream, x, ldx, M, k_main, T, Kpad, N, k_chunk, dst, ldo, xrows);    \
+        break;                                                                                    \
+      }                                                                                           \
       if ((M & 1) == 0) {   /* gene pairs per lane (4-byte loads) */                               \
         if (nw == 8)                                                                              \
           hipLaunchKernelGGL((count_gemm_dw_kernel<NT_, XT, true, false, 8>), grid, dim3(512), 0, \
@@ -783,8 +397,13 @@ static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, i
   const size_t total = (size_t)M * N;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(count_gemm_reduce_kernel<XT>, dim3(blocks), dim3(256), 0, stream, slabs, bias,
-                     C, M, N, ldc, splits, act, mode, x, ldx, other, ld_other, k_main, K);
+  if (xrows)
+    hipLaunchKernelGGL(count_gemm_reduce_rows_kernel, dim3(blocks), dim3(256), 0, stream, slabs,
+                       bias, C, M, N, ldc, splits, act, mode, reinterpret_cast<const uint16_t*>(x),
+                       ldx, other, ld_other, k_main, K, xrows);
+  else
+    hipLaunchKernelGGL(count_gemm_reduce_kernel<XT>, dim3(blocks), dim3(256), 0, stream, slabs,
+                       bias, C, M, N, ldc, splits, act, mode, x, ldx, other, ld_other, k_main, K);
   SCVAE_LAUNCH_CHECK("count_gemm_reduce_kernel");
   return 0;
 }
@@ -798,9 +417,9 @@ int count_gemm(hipStream_t stream, int mode, const float* x, int ldx, int rows, 
 
 int count_gemm_u16(hipStream_t stream, int mode, const uint16_t* x, int ldx, int rows, int cols,
                    const float* other, int ld_other, int N, const float* bias, int act, float* C,
-                   int ldc, void* workspace, size_t workspace_bytes) {
+                   int ldc, void* workspace, size_t workspace_bytes, const int64_t* x_rows) {
   return count_gemm_impl<uint16_t>(stream, mode, x, ldx, rows, cols, other, ld_other, N, bias, act,
-                                   C, ldc, workspace, workspace_bytes);
+                                   C, ldc, workspace, workspace_bytes, x_rows);
 }
 
 // ====================== the minibatch as tile-indexed non-zeros ======================

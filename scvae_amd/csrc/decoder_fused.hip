@@ -729,14 +729,19 @@ static int launch_decoder(hipStream_t s, int kind, const float* d, int rows, int
                           int F, Targets t, int B, const float* gw, int inline_lgamma,
                           float* ll_part, float* dd_part, int arith, float* planes = nullptr,
                           const HeadDropout* drop = nullptr, int dd_mode = 0,
-                          float* rg_slab = nullptr) {
+                          float* rg_slab = nullptr, const int64_t* t_rows = nullptr) {
   const int P = likelihood_heads(kind);
   if (TRAIN && planes && decoder_train_kernel(P, H, arith) == 3) {
     static const int dbg = [] { const char* e = getenv("SCVAE_D3_DEBUG"); return e ? atoi(e) : 0; }();
     return decoder_fused3_launch(s, true, kind, d, rows, H, hp, F, t, B, gw,
                                  inline_lgamma | (dbg << 8), ll_part, dd_part, planes, drop, 0,
                                  nullptr, (dd_mode & 1) | (arith == 2 ? 2 : 0) | (dd_mode & 4),
-                                 rg_slab);
+                                 rg_slab, t_rows);
+  }
+  if (t_rows) {
+    set_error("targets through a row index: the bf16x9 head kernels and decoder_forward_kernel "
+              "only");
+    return -1;
   }
   if (drop) {
     set_error("head dropout inside the fused kernel needs the bf16x9 head kernel");
@@ -770,10 +775,33 @@ static int launch_decoder(hipStream_t s, int kind, const float* d, int rows, int
   return 0;
 }
 
+// Which kernel a forward-only call takes (SCVAE_DECODER_FORWARD overrides, for A/B runs):
+//   3  the forward instantiation of the bf16x9 training kernel (decoder_fused3.hip) -- default
+//      for one- and two-head likelihoods under the bf16x9 head arithmetic;
+//   1  the register-resident fp32 forward kernel (decoder_forward.hip) -- default otherwise,
+//      where its LDS budget allows;
+//   0  the forward instantiation of the fp32 training kernels;
+//   4  (odd widths, widths beyond 126, bf16x9 arithmetic) decoder_head4_kernel<.., FWD = true>.
+// (Also what scvae_plan_accepts_counts_rows asks: kernels 1, 3 and 4 read their targets through
+//  a row index, 0 does not.)
+int decoder_forward_choice(int heads, int H, int arith) {
+  static const int forced = [] {
+    const char* e = getenv("SCVAE_DECODER_FORWARD");
+    return (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : -1;
+  }();
+  int which = decoder_forward_supported(heads, H) ? 1 : 0;
+  if (arith >= 1 && heads <= 2 && decoder_fused3_supported(heads, H)) which = 3;
+  if (forced == 0) which = 0;
+  if (forced == 1 && decoder_forward_supported(heads, H)) which = 1;
+  if (!decoder_fused_supported(H)) which = 4;
+  if (forced == 4 && arith >= 1 && decoder_fused4_supported(heads, H)) which = 4;
+  return which;
+}
+
 // Forward only (is_training=False / importance-weight pass): ll[rows]
 int decoder_fused_forward(hipStream_t s, int kind, const float* d, int rows, int H, HeadParams hp,
                           int F, Targets t, int B, const float* row_const, float* ll,
-                          float* workspace, int arith) {
+                          float* workspace, int arith, const int64_t* t_rows) {
   const int heads = likelihood_heads(kind);
   // (odd widths and widths beyond 126: the forward half of the producer / consumer kernel)
   const bool wide = !decoder_fused_supported(H);
@@ -785,43 +813,27 @@ int decoder_fused_forward(hipStream_t s, int kind, const float* d, int rows, int
   // (the data-only term lgamma(1 + t) of the count likelihoods: the caller's row constant, or
   //  evaluated inline; the Bernoulli likelihood has none)
   const int inline_lgamma = (row_const || kind == LK_BERNOULLI) ? 0 : 1;
-  // Which kernel (SCVAE_DECODER_FORWARD overrides, for A/B runs):
-  //   3  the forward instantiation of the bf16x9 training kernel (decoder_fused3.hip) -- default
-  //      for one- and two-head likelihoods under the bf16x9 head arithmetic;
-  //   1  the register-resident fp32 forward kernel (decoder_forward.hip) -- default otherwise,
-  //      where its LDS budget allows;
-  //   0  the forward instantiation of the fp32 training kernels;
-  //   4  (odd widths, widths beyond 126, bf16x9 arithmetic) decoder_head4_kernel<.., FWD = true>.
   // The workspace is the one decoder_fused_workspace_floats(.., train = true) sizes (the plans
   // and the C ABI size no other): the bf16 planes of d go behind ll_part.
-  static const int forced = [] {
-    const char* e = getenv("SCVAE_DECODER_FORWARD");
-    return (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : -1;
-  }();
-  int which = decoder_forward_supported(heads, H) ? 1 : 0;
-  if (arith >= 1 && heads <= 2 && decoder_fused3_supported(heads, H)) which = 3;
-  if (forced == 0) which = 0;
-  if (forced == 1 && decoder_forward_supported(heads, H)) which = 1;
-  if (wide) which = 4;
-  if (forced == 4 && arith >= 1 && decoder_fused4_supported(heads, H)) which = 4;
+  const int which = decoder_forward_choice(heads, H, arith);
   int rc;
   if (which == 4) {
     const int bn = d4_strip_genes(heads, H);
     strips = (F + bn - 1) / bn;
     float* planes = workspace + ((size_t)strips * rows + 63) / 64 * 64;
     rc = decoder_fused3_launch(s, false, kind, d, rows, H, hp, F, t, B, nullptr, inline_lgamma,
-                               ll_part, nullptr, planes, nullptr, 0, nullptr, 8);
+                               ll_part, nullptr, planes, nullptr, 0, nullptr, 8, nullptr, t_rows);
   } else if (which == 3) {
     const int bn = decoder_fused3_strip_genes(heads);
     strips = (F + bn - 1) / bn;
     float* planes = workspace + ((size_t)strips * rows + 63) / 64 * 64;
     rc = decoder_fused3_launch(s, false, kind, d, rows, H, hp, F, t, B, nullptr, inline_lgamma,
-                               ll_part, nullptr, planes);
+                               ll_part, nullptr, planes, nullptr, 0, nullptr, 0, nullptr, t_rows);
   } else if (which == 1) {
-    rc = decoder_forward_launch(s, kind, d, rows, H, hp, F, t, B, inline_lgamma, ll_part);
+    rc = decoder_forward_launch(s, kind, d, rows, H, hp, F, t, B, inline_lgamma, ll_part, t_rows);
   } else {
     rc = launch_decoder<false>(s, kind, d, rows, H, hp, F, t, B, nullptr, inline_lgamma, ll_part,
-                               nullptr, arith);
+                               nullptr, arith, nullptr, nullptr, 0, nullptr, t_rows);
   }
   if (rc) return rc;
   hipLaunchKernelGGL(ll_reduce_kernel, dim3((rows + 15) / 16), dim3(1024), 0, s, ll_part, strips,
@@ -931,7 +943,7 @@ int decoder_fused_cpoisson(hipStream_t s, bool train, const float* d, int rows, 
 int decoder_fused_train(hipStream_t s, int kind, const float* d, int rows, int H, HeadParams hp,
                         int F, Targets t, int B, const float* gw, const float* row_const,
                         float* ll, float* dd, float* workspace, int arith, bool kernel_only,
-                        const HeadDropout* drop, int dd_mode) {
+                        const HeadDropout* drop, int dd_mode, const int64_t* t_rows) {
   const int heads = likelihood_heads(kind);
   SCVAE_ARG(d && t.p && gw && ll && dd && workspace &&
             decoder_fused_train_supported(heads, H, arith));
@@ -957,7 +969,7 @@ int decoder_fused_train(hipStream_t s, int kind, const float* d, int rows, int H
   const bool no_lgamma = kind == LK_BERNOULLI || kind == LK_CAT2 || kind == LK_CAT3;
   int rc = launch_decoder<true>(s, kind, d, rows, H, hp, F, t, B, gw,
                                 (row_const || no_lgamma) ? 0 : 1, ll_part, dd_part,
-                                arith, planes, drop, dd_mode, rg_slab);
+                                arith, planes, drop, dd_mode, rg_slab, t_rows);
   if (rc) return rc;
   if (kernel_only) return 0;  // profiling aid: leave the per-strip partials unreduced
   hipLaunchKernelGGL(ll_reduce_kernel, dim3((rows + 15) / 16), dim3(1024), 0, s, ll_part,

@@ -262,607 +262,34 @@ __device__ __forceinline__ float select_n(const float (&v)[4], const IndexMasks3
 //          -> cp.out2;
 //   CP = 2 (forward, given cp.lse): the strip's part of sum_f log p(t_f) -> ll_part, of S -> cp.out2;
 //   CP = 3 (training, given cp.lse and cp.S): G = gw (gate (t - N lambda) - lambda S), phase B.
+//
+// IDX (decoder_head3_rows_kernel): the targets are rows of a RESIDENT uint16 matrix, cell b of the
+// minibatch its row trows[b].  A lane fetches the index of its row of tile i + 2 right behind its
+// request for the targets of tile i + 1 (which use the index fetched a tile earlier), so the
+// dependent load is off the chain; rows beyond R read the index of row R - 1.
 template <int KIND, int KS1, bool U16, bool TRAIN, bool DROP, int CP>
 __global__ __launch_bounds__(D3_THREADS) void decoder_head3_kernel(
     const uint16_t* __restrict__ dA, const uint16_t* __restrict__ dT, int R, int Rpad, int H,
     HeadParams hp, int F, Targets tg, int B, const float* __restrict__ gw, int inline_lgamma,
     float* __restrict__ ll_part, float* __restrict__ dd_part,
     const uint32_t* __restrict__ drop_bits, float inv_keep, CpRows cp) {
-  static_assert(TRAIN || !DROP, "dropout is a training-time operation");
-  static_assert((CP > 0) == (KIND == LK_CPOISSON), "CP selects the passes of LK_CPOISSON");
-  static_assert(CP == 0 || ((CP == 3) == TRAIN && !DROP), "CP 1 / 2 forward, CP 3 training");
-  using Traits = LikelihoodTraits<KIND>;
-  constexpr int P = Traits::P;
-  constexpr int BN = d3_bn(P), ROWB = d3_rowb(P);
-  constexpr int GPLANE = D3_BM * ROWB;      // bytes of one [64 rows][BN genes] plane of G
-  constexpr int NSB = BN / 32;              // 16-gene blocks of a wave in phase A (2 / 1)
-  constexpr int NE = 4 * NSB;               // elements of a lane
-  constexpr bool KSPLIT = P >= 3;           // GEMM2 splits the tile's rows between wave pairs
-  constexpr int KS2 = KSPLIT ? 2 : 4;       // 16-row k-steps of GEMM2 per wave
-  constexpr int KS3 = BN / 16;              // 16-gene k-steps of GEMM3 per head
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int HP1 = d3_hp1(H);
-  const int WPLANE = HP1 * ROWB;                    // bytes of one [HP1][BN] plane of W
-  char* Wl = smem;                                  // [P][3][HP1][BN + 8] bf16
-  char* Gl = smem + (size_t)P * 3 * WPLANE;         // [P][3][64][BN + 8] bf16
-  float* llbuf = reinterpret_cast<float*>(Gl + (size_t)P * 3 * GPLANE);   // [2][64]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = lane >> 4, i16 = lane & 15, li = lane & 31, kh = lane >> 5;
-  const int c0 = blockIdx.x * BN;
-
-  // ---- LDS: zero everything (padding and over-read regions must hold finite values), then the
-  //      strip's weights and biases, cut into planes.  ALL of a thread's weight loads -- its rows
-  //      of every head -- are requested first, from clamped, always valid addresses, and land
-  //      under the zero fill: as a plain loop this fill was one dependent global-memory round trip
-  //      per weight row, 12 us per workgroup -- a third of the kernel at a 100-cell minibatch ----
-  constexpr int HSTEP = D3_THREADS / BN;
-  constexpr int NV = (126 + HSTEP) / HSTEP;            // rows 0 .. H <= 126 of a thread
-  {
-    const int g = tid & (BN - 1), h0 = tid / BN;
-    const bool col_ok = c0 + g < F;
-    const int gc = min(c0 + g, F - 1);
-    float v[P][NV];
-    // (the plain [H, F] layout, or -- the class logits of the P_K head -- genes gene_stride apart
-    //  in rows of row_pitch elements)
-    const size_t gs = hp.gene_stride ? hp.gene_stride : 1;
-    const size_t rp = hp.row_pitch ? hp.row_pitch : F;
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      const float* wj = hp.W[j] + gc * gs;
-      const float* bj = hp.b[j] + gc * gs;
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int h = h0 + u * HSTEP;
-        const float* src = h < H ? wj + (size_t)h * rp : bj;
-        v[j][u] = *src;
-      }
-    }
-    {
-      const int n16 = (int)(((size_t)P * 3 * WPLANE + (size_t)P * 3 * GPLANE + 2 * D3_BM * 4) / 16);
-      u32x4* z = reinterpret_cast<u32x4*>(smem);
-      for (int i = tid; i < n16; i += D3_THREADS) z[i] = u32x4{0u, 0u, 0u, 0u};
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int h = h0 + u * HSTEP;
-        if (h <= H) {
-          unsigned b1, b2, b3;
-          split3_rn(col_ok ? v[j][u] : 0.f, b1, b2, b3);
-          char* dst = Wl + (size_t)(j * 3) * WPLANE + h * ROWB + 2 * g;
-          *reinterpret_cast<uint16_t*>(dst) = (uint16_t)(b1 >> 16);
-          *reinterpret_cast<uint16_t*>(dst + WPLANE) = (uint16_t)(b2 >> 16);
-          *reinterpret_cast<uint16_t*>(dst + 2 * WPLANE) = (uint16_t)(b3 >> 16);
-        }
-      }
-  }
-  __syncthreads();
-
-  // ---- wave roles ----
-  const int gp = w & 1, rq = w >> 1;        // phase A: genes 16 NSB gp .., rows 16 rq .. of the tile
-  const int ht = w & 3, hi2 = w >> 2;       // phase B: h tile; GEMM3: row tile hi2; GEMM2: gene
-                                            // tile hi2 (all 64 rows), or -- three heads -- rows
-                                            // 32 hi2 .. (all 32 genes)
-  const int n_ht3 = (H + 31) / 32, n_ht2 = (H + 1 + 31) / 32;
-  const int nb16 = Rpad / 16;               // 16-row blocks of the planes of d
-
-  // per-lane byte offsets
-  const int gbase = 16 * NSB * gp;
-  const int trw = (8 * q + (i16 >> 2)) * ROWB + 2 * (gbase + 4 * (i16 & 3));        // W, GEMM1
-  const int gst = (16 * rq + i16) * ROWB + 2 * (gbase + 4 * q);                     // G store
-  const int g3a = (32 * hi2 + li) * ROWB + 16 * kh;                                 // G, GEMM3 A
-  const int g3b = (32 * ht + li) * ROWB + 16 * kh;                                  // W, GEMM3 B
-  const int g2b = ((KSPLIT ? 32 * hi2 : 0) + 8 * (q >> 1) + (i16 >> 2)) * ROWB +
-                  2 * ((KSPLIT ? 0 : 32 * hi2) + 16 * (q & 1) + 4 * (i16 & 3));     // G, GEMM2 B
-
-  f32x16 accW[P];                           // dW tile (h tile ht [, gene tile hi2]) of every head
-#pragma unroll
-  for (int j = 0; j < P; ++j)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) accW[j][i] = 0.f;
-
-  const int n_tiles = (R + D3_BM - 1) / D3_BM;
-  const size_t dplane = (size_t)Rpad * D3_KP;
-
-  // targets / upstream of a tile, in flight from the previous phase B (returned by value: an
-  // array written through a reference capture ends up in scratch memory)
-  struct TileIn { f32x4m t[NSB]; float up0; float cpn, cpl, cps; };
-  auto load_t = [&](int m0) {
-    TileIn in;
-    const int row = m0 + 16 * rq + i16;
-    const bool rok = row < R;
-    in.up0 = (TRAIN && rok) ? gw[row] : 0.f;
-    const int rc = rok ? row : R - 1;
-    const int cell = R == B ? rc : rc % B;
-    in.cpn = in.cpl = in.cps = 0.f;
-    if (CP > 0) in.cpn = cp.count_sum[cell];
-    if (CP >= 2) in.cpl = cp.lse[rc];
-    if (CP == 3) in.cps = cp.S[rc];
-    const size_t trow = (size_t)cell * tg.ld;
-#pragma unroll
-    for (int sb = 0; sb < NSB; ++sb) {
-      const int c = c0 + gbase + 16 * sb + 4 * q;
-      f32x4m v = {0.f, 0.f, 0.f, 0.f};
-      if (U16) {        // pitch % 8 == 0, padding columns zero: one 8-byte load
-        const uint16_t* tp = static_cast<const uint16_t*>(tg.p) + trow + c;
-        const u32x2 u = *reinterpret_cast<const u32x2*>(tp);
-        v.x = __uint_as_float(u.x); v.y = __uint_as_float(u.y);
-      } else {
-        const float* tp = static_cast<const float*>(tg.p) + trow + c;
-        if (c + 3 < F) {
-          const f32x4u u = *reinterpret_cast<const f32x4u*>(tp);
-          v.x = u.x; v.y = u.y; v.z = u.z; v.w = u.w;
-        } else {
-          v.x = (c < F) ? tp[0] : 0.f;
-          v.y = (c + 1 < F) ? tp[1] : 0.f;
-          v.z = (c + 2 < F) ? tp[2] : 0.f;
-        }
-      }
-      in.t[sb] = v;
-    }
-    return in;
-  };
-  TileIn nxt = load_t(0);
-  // d fragments of GEMM1 (B[k = h][n = row]): 3 planes per k-step, one contiguous KiB each,
-  // requested one k-step ahead of the MFMAs that use them (k-step 0 of a tile during the
-  // previous phase B)
-  const size_t dset = DROP ? d3_set_elems(Rpad) : 0;     // plane set of head j: + j * dset
-  auto load_d1 = [&](int m0, int ks, bf16x8 (&dst)[3], int j = 0) {
-    const uint16_t* dbase = dA + j * dset + ((size_t)(m0 / 16 + rq) * 4 + ks) * 512 + lane * 8;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) dst[pl] = global_b128(dbase + pl * dplane);
-  };
-  // (DROP: contraction steps st = k-step * P + head; steps 0 and 1 of a tile travel under the
-  //  previous phase B)
-  constexpr int NST1 = KS1 * P;
-  bf16x8 bfr0[3], bfr1[3];
-  load_d1(0, 0, bfr0);
-  if (DROP) { if (NST1 > 1) load_d1(0, 1 / P, bfr1, 1 % P); }
-  else if (D3_AHEAD > 1 && KS1 > 1) load_d1(0, 1, bfr1);
-
-  for (int tile = 0; tile < n_tiles; ++tile) {
-    const int m0 = tile * D3_BM;
-    const TileIn cur = nxt;
-    const float up = cur.up0;
-    // row sums of the tile (forward only: alternating with the unused G area)
-    // (not at the start of the G area: GEMM1's last k-step reads up to 16 rows past the last
-    //  weight plane -- times zero columns of d, but a row sum's low half can be a bf16 NaN)
-    float* lb = (!TRAIN && (tile & 1)) ? reinterpret_cast<float*>(Gl + 4096) : llbuf;
-    float* lb2 = reinterpret_cast<float*>(Gl + ((tile & 1) ? 12288 : 8192));   // (CP 1 / 2)
-    // =================== phase A: GEMM1 (transposed) + likelihood + G -> LDS ===================
-    f32x4m acc1[P][NSB];
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-      for (int sb = 0; sb < NSB; ++sb) acc1[j][sb] = f32x4m{0.f, 0.f, 0.f, 0.f};
-    if constexpr (DROP) {
-      // one head per step: its W fragments one step ahead, its d fragments two
-      bf16x8 afr[2][NSB][3], bfr[3][3];
-      auto load_wj = [&](int st, bf16x8 (&dst)[NSB][3]) {
-        const int ks = st / P, j = st % P;
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl)
-            dst[sb][pl] = lds_tr8<ROWB>(Wl + (size_t)(j * 3 + pl) * WPLANE + trw + 32 * sb +
-                                        32 * ks * ROWB);
-      };
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) { bfr[0][pl] = bfr0[pl]; bfr[1][pl] = bfr1[pl]; }
-      load_wj(0, afr[0]);
-#pragma unroll
-      for (int st = 0; st < NST1; ++st) {
-        if (st + 2 < NST1) {
-          load_d1(m0, (st + 2) / P, bfr[(st + 2) % 3], (st + 2) % P);
-          d3_pin_loads();
-        }
-        if (st + 1 < NST1) load_wj(st + 1, afr[(st + 1) & 1]);
-        const int j = st % P;
-#pragma unroll
-        for (int a = 2; a >= 0; --a)
-#pragma unroll
-          for (int b = 2; b >= 0; --b)
-#pragma unroll
-            for (int sb = 0; sb < NSB; ++sb)
-              acc1[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  afr[st & 1][sb][a], bfr[st % 3][b], acc1[j][sb], 0, 0, 0);
-      }
-    } else {
-      // W fragments (transpose reads) and d fragments one k-step ahead of the MFMAs
-      bf16x8 afr[2][P][NSB][3], bfr[D3_NB][3];
-      auto load_w = [&](int ks, bf16x8 (&dst)[P][NSB][3]) {
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-#pragma unroll
-          for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-              dst[j][sb][pl] = lds_tr8<ROWB>(Wl + (size_t)(j * 3 + pl) * WPLANE + trw + 32 * sb +
-                                             32 * ks * ROWB);
-      };
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) bfr[0][pl] = bfr0[pl];
-      if (D3_AHEAD > 1 && KS1 > 1) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) bfr[1][pl] = bfr1[pl];
-      }
-      load_w(0, afr[0]);
-#pragma unroll
-      for (int ks = 0; ks < KS1; ++ks) {
-        if (ks + D3_AHEAD < KS1) {
-          load_d1(m0, ks + D3_AHEAD, bfr[(ks + D3_AHEAD) % D3_NB]);
-          d3_pin_loads();
-        }
-        if (ks + 1 < KS1) load_w(ks + 1, afr[(ks + 1) & 1]);
-        if (!TRAIN && ks == KS1 - 1) {
-          // (forward only) the next tile's targets and first d fragments: under this k-step
-          // and the likelihood.  Unconditional -- the last tile requests itself again: under
-          // a branch the compiler waits for the loads where the arms meet
-          const int mn = min(m0 + D3_BM, Rpad - D3_BM);
-          nxt = load_t(mn);
-          load_d1(mn, 0, bfr0);
-          if (D3_AHEAD > 1 && KS1 > 1) load_d1(mn, 1, bfr1);
-          d3_pin_loads();
-        }
-        // small terms first; the accumulators (head x gene block) are independent chains
-#pragma unroll
-        for (int a = 2; a >= 0; --a)
-#pragma unroll
-          for (int b = 2; b >= 0; --b)
-#pragma unroll
-            for (int j = 0; j < P; ++j)
-#pragma unroll
-              for (int sb = 0; sb < NSB; ++sb)
-                acc1[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    afr[ks & 1][j][sb][a], bfr[ks % D3_NB][b], acc1[j][sb], 0, 0, 0);
-      }
-    }
-    // ---- likelihood of this lane's NSB x 4 elements: row 16 rq + i16, genes
-    //      16 NSB gp + 16 sb + 4 q + e ----
-    float G[P][NE], tval[NE];
-    float lsum = 0.f, lsum2 = 0.f;
-    unsigned nz = 0;
-    if constexpr (CP > 0) {
-      // ---- constrained Poisson: this lane's NE logits of ONE row ----
-      const float cpn = cur.cpn, cpl = cur.cpl, cps = cur.cps;
-      float av[NE];
-      bool okv[NE];
-#pragma unroll
-      for (int sb = 0; sb < NSB; ++sb) {
-        if (U16) {
-          const unsigned v0 = __float_as_uint(cur.t[sb][0]), v1 = __float_as_uint(cur.t[sb][1]);
-          tval[4 * sb] = (float)(v0 & 0xFFFFu); tval[4 * sb + 1] = (float)(v0 >> 16);
-          tval[4 * sb + 2] = (float)(v1 & 0xFFFFu); tval[4 * sb + 3] = (float)(v1 >> 16);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) tval[4 * sb + e] = cur.t[sb][e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          av[4 * sb + e] = acc1[0][sb][e];
-          okv[4 * sb + e] = c0 + gbase + 16 * sb + 4 * q + e < F;
-        }
-      }
-      if (CP == 1) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NE; ++i) mx = fmaxf(mx, okv[i] ? av[i] : -INFINITY);
-        float se = 0.f;
-#pragma unroll
-        for (int i = 0; i < NE; ++i) se += okv[i] ? __expf(av[i] - mx) : 0.f;
-        float m2 = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-        m2 = fmaxf(m2, __shfl_xor(m2, 32, WAVE));
-        se = mx > -INFINITY ? se * __expf(mx - m2) : 0.f;
-        lsum = m2;
-        lsum2 = se;     // (summed over the wave's gene groups below)
-      } else {
-        const float log_n = __logf(fmaxf(cpn, F32_TINY));
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-          const float tv = tval[i];
-          const float log_lam = av[i] - cpl;
-          const float lam = __expf(log_lam);
-          const bool gate = lam >= F32_TINY;
-          const float own = gate ? tv - cpn * lam : 0.f;
-          if (CP == 2) {
-            const float lam_c = gate ? lam : F32_TINY;
-            const float log_rate = (gate ? log_lam : LOG_F32_TINY) + log_n;
-            lsum += okv[i] ? (tv > 0.f ? tv * log_rate : 0.f) - lam_c * cpn : 0.f;
-            lsum2 += okv[i] ? own : 0.f;
-            nz |= (okv[i] && tv > 0.f) ? (1u << i) : 0u;
-          } else {
-            G[0][i] = up * (own - lam * cps);
-          }
-        }
-      }
-    } else {
-#pragma unroll
-    for (int sb = 0; sb < NSB; ++sb) {
-      if (U16) {
-        const unsigned v0 = __float_as_uint(cur.t[sb][0]), v1 = __float_as_uint(cur.t[sb][1]);
-        tval[4 * sb] = (float)(v0 & 0xFFFFu); tval[4 * sb + 1] = (float)(v0 >> 16);
-        tval[4 * sb + 2] = (float)(v1 & 0xFFFFu); tval[4 * sb + 3] = (float)(v1 >> 16);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tval[4 * sb + e] = cur.t[sb][e];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float a[P], g[P], lp, r, rgate;
-#pragma unroll
-        for (int j = 0; j < P; ++j) a[j] = acc1[j][sb][e];
-        // (tg.shift > 0 -- the count part of the piecewise categorical likelihood: the
-        //  distribution sees t - shift where t >= shift, nothing elsewhere; 0: every element)
-        const bool live = tval[4 * sb + e] >= tg.shift;
-        tval[4 * sb + e] = live ? tval[4 * sb + e] - tg.shift : 0.f;
-        lik_dense<KIND, TRAIN>(tval[4 * sb + e], a, lp, g, r, rgate);
-        const bool ok = live && c0 + gbase + 16 * sb + 4 * q + e < F;
-        lsum += ok ? lp : 0.f;
-        if (TRAIN) {
-#pragma unroll
-          for (int j = 0; j < P; ++j) G[j][4 * sb + e] = live ? up * g[j] : 0.f;
-        }
-        nz |= (ok && tval[4 * sb + e] > 0.f) ? (1u << (4 * sb + e)) : 0u;
-      }
-    }
-    }
-    // ---- t > 0: + lgamma(r+t) - lgamma(r) [- lgamma(1+t)], and the digamma term of dlog r:
-    //      a per-lane walk over the lane's non-zero elements ----
-    if (Traits::HAS_R || (inline_lgamma && (CP == 0 || CP == 2))) {
-      float lr[NE];
-      if (Traits::HAS_R) {
-#pragma unroll
-        for (int i = 0; i < NE; ++i) lr[i] = acc1[P - 1][i >> 2][i & 3];
-      }
-      while (__builtin_amdgcn_ballot_w64(nz != 0) != 0) {
-        const bool on = nz != 0;
-        const int idx = on ? __builtin_ctz(nz) : 0;
-        nz &= nz - 1;
-        const IndexMasks3 km = index_masks3(idx);
-        const float tt = select_n(tval, km);
-        float corr = 0.f;
-        if (Traits::HAS_R) {
-          const float lrv = select_n(lr, km);
-          const float r = __expf(fminf(fmaxf(lrv, -10.f), 10.f));
-          const float rgate = (lrv >= -10.f && lrv <= 10.f) ? 1.f : 0.f;
-          const bool small = !on || (tt <= 8.f && tt == __builtin_rintf(tt));
-          float A, D;
-          if (__builtin_amdgcn_ballot_w64(!small) == 0)
-            lgamma_digamma_diff_small_wave<TRAIN>(r, on ? tt : 0.f, A, D);
-          else
-            lgamma_digamma_diff_general<TRAIN>(r, on ? tt : 1.f, A, D);
-          corr = A;
-          // (zero-inflated: at t > 0 the gradient of the base distribution passes unscaled,
-          //  zero_inflated.py:194-199 -- the same insertion)
-          if (TRAIN) {
-            const float delta = on ? up * rgate * r * D : 0.f;
-#pragma unroll
-            for (int e = 0; e < NE; ++e) G[P - 1][e] += (idx == e) ? delta : 0.f;
-          }
-        }
-        if (inline_lgamma) corr -= lgamma1p(tt);
-        lsum += on ? corr : 0.f;
-      }
-    }
-    // ---- row sums over this wave's genes -> llbuf[gp][row] ----
-    if (CP == 1) {
-      // (maximum already common to the wave's gene groups; the sums of exponentials refer to it)
-      float se = lsum2;
-      se += __shfl_xor(se, 16, WAVE);
-      se += __shfl_xor(se, 32, WAVE);
-      if (q == 0) {
-        lb[gp * D3_BM + 16 * rq + i16] = lsum;
-        lb2[gp * D3_BM + 16 * rq + i16] = se;
-      }
-    } else if (CP != 3) {
-      float sm = lsum;
-      sm += __shfl_xor(sm, 16, WAVE);
-      sm += __shfl_xor(sm, 32, WAVE);
-      if (q == 0) lb[gp * D3_BM + 16 * rq + i16] = sm;
-      if (CP == 2) {
-        float s2 = lsum2;
-        s2 += __shfl_xor(s2, 16, WAVE);
-        s2 += __shfl_xor(s2, 32, WAVE);
-        if (q == 0) lb2[gp * D3_BM + 16 * rq + i16] = s2;
-      }
-    }
-    // ---- G_j -> three bf16 planes, row-major [row][gene], 8 bytes (4 genes) per store ----
-    if (TRAIN) {
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-      for (int sb = 0; sb < NSB; ++sb) {
-        unsigned p1[2], p2[2], p3[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-          split3_rn_pair(G[j][4 * sb + 2 * e], G[j][4 * sb + 2 * e + 1], p1[e], p2[e], p3[e]);
-        char* dst = Gl + (size_t)(j * 3) * GPLANE + gst + 32 * sb;
-        *reinterpret_cast<u32x2*>(dst) = u32x2{p1[0], p1[1]};
-        *reinterpret_cast<u32x2*>(dst + GPLANE) = u32x2{p2[0], p2[1]};
-        *reinterpret_cast<u32x2*>(dst + 2 * GPLANE) = u32x2{p3[0], p3[1]};
-      }
-    }
-    lds_barrier();
-
-    // =================== phase B: GEMM3 (LDS operands), then GEMM2 ===================
-    // per-row log-likelihood of the strip: the two gene blocks summed in a fixed order
-    if (CP == 1) {
-      // the two gene halves: common maximum, sums of exponentials rescaled to it
-      if (tid < D3_BM && m0 + tid < R) {
-        const float ma = lb[tid], mb = lb[D3_BM + tid];
-        const float m = fmaxf(ma, mb);
-        const float se = (ma > -INFINITY ? lb2[tid] * __expf(ma - m) : 0.f) +
-                         (mb > -INFINITY ? lb2[D3_BM + tid] * __expf(mb - m) : 0.f);
-        ll_part[(size_t)blockIdx.x * R + m0 + tid] = m;
-        cp.out2[(size_t)blockIdx.x * R + m0 + tid] = se;
-      }
-    } else if (CP != 3) {
-      if (tid < D3_BM && m0 + tid < R) {
-        ll_part[(size_t)blockIdx.x * R + m0 + tid] = lb[tid] + lb[D3_BM + tid];
-        if (CP == 2) cp.out2[(size_t)blockIdx.x * R + m0 + tid] = lb2[tid] + lb2[D3_BM + tid];
-      }
-    }
-    if (!TRAIN) continue;   // (the next tile writes the other row-sum buffer: no second barrier)
-    // GEMM2's d fragments (A[i = h][k = row]) come from L2 one k-step ahead; k-step 0 is
-    // requested here and lands under GEMM3
-    auto load_a2 = [&](int ks, bf16x8 (&dst)[3], int j = 0) {
-      const uint16_t* tb = dT + j * dset +
-          ((size_t)ht * nb16 + m0 / 16 + (KSPLIT ? 2 * hi2 : 0) + ks) * 512 + lane * 8;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) dst[pl] = global_b128(tb + pl * dplane);
-    };
-    constexpr int NST2 = KS2 * P;              // (DROP: steps (k-step, head), two ahead)
-    bf16x8 a2[DROP ? 3 : D3_NB][3];
-    if (ht < n_ht2) {
-      load_a2(0, a2[0]);
-      if (DROP) { if (NST2 > 1) load_a2(1 / P, a2[1], 1 % P); }
-      else if (D3_AHEAD > 1 && KS2 > 1) load_a2(1, a2[1]);
-    }
-    // (DROP) the heads' mask words of this lane's row and h tile, shifted to its four-h groups
-    uint32_t mw[P];
-    if (DROP) {
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-        mw[j] = ht < n_ht3
-                    ? drop_bits[((size_t)j * Rpad + m0 + 32 * hi2 + li) * 4 + ht] >> (4 * kh)
-                    : 0u;
-    }
-    // next tile's targets
-    if (tile + 1 < n_tiles) nxt = load_t(m0 + D3_BM);
-    if (ht < n_ht3) {
-      // ---- GEMM3: dd[row, h] = sum_j sum_gene G_j[row, gene] W_j[h, gene] ----
-      f32x16 acc3, accS;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { acc3[i] = 0.f; accS[i] = 0.f; }
-      bf16x8 af[2][3], bf[2][3];
-      auto load_3 = [&](int st, bf16x8 (&a)[3], bf16x8 (&b)[3]) {   // step = head * KS3 + k-step
-        const int j = st / KS3, ks = st % KS3;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          a[pl] = lds_b128(Gl + (size_t)(j * 3 + pl) * GPLANE + g3a + 32 * ks);
-          b[pl] = lds_b128(Wl + (size_t)(j * 3 + pl) * WPLANE + g3b + 32 * ks);
-        }
-      };
-      load_3(0, af[0], bf[0]);
-#pragma unroll
-      for (int st = 0; st < KS3 * P; ++st) {
-        if (st + 1 < KS3 * P) load_3(st + 1, af[(st + 1) & 1], bf[(st + 1) & 1]);
-#pragma unroll
-        for (int a = 2; a >= 0; --a)
-#pragma unroll
-          for (int b = 2; b >= 0; --b)
-            acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[st & 1][b], af[st & 1][a], acc3, 0,
-                                                           0, 0);
-        if (DROP && st % KS3 == KS3 - 1) {
-          // head st / KS3 is complete: through its mask (element i = 4 c + e <-> h = 32 ht +
-          // 8 c + 4 kh + e), times 1 / keep, into the sum over the heads
-          const uint32_t m = mw[st / KS3];
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            accS[i] += ((m >> (8 * (i >> 2) + (i & 3))) & 1u) ? acc3[i] * inv_keep : 0.f;
-            acc3[i] = 0.f;
-          }
-        }
-      }
-      if (DROP) acc3 = accS;
-      // (computed transposed, dd^T[h, row]: a lane holds, for each of four groups, FOUR consecutive
-      //  h of one row.  The per-strip partial goes to a slab [strip][H / 4][R][4]: one 16-byte
-      //  store per group and lane, 32 consecutive rows of an h quad = 512 contiguous bytes per
-      //  half wave -- whole lines, a quarter of the store instructions of an [H][R] slab, which
-      //  in turn beat the row-major slab with its 100-float rows in partial lines.
-      //  Non-temporal: the slabs are read exactly once, by dd_reduce_q_kernel)
-      const int row = m0 + 32 * hi2 + li;
-      if (row < R) {
-        const int HQ = (H + 3) >> 2;
-        f32x4m* dst = reinterpret_cast<f32x4m*>(dd_part) +
-                      ((size_t)blockIdx.x * HQ + 8 * ht + kh) * R + row;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (4 * (8 * ht + 2 * c + kh) < H)
-            __builtin_nontemporal_store(
-                f32x4m{acc3[4 * c], acc3[4 * c + 1], acc3[4 * c + 2], acc3[4 * c + 3]},
-                dst + (size_t)2 * c * R);
-        }
-      }
-    }
-    // the next tile's d fragments of GEMM1: in flight under GEMM2 and the barrier
-    if (tile + 1 < n_tiles) {
-      load_d1(m0 + D3_BM, 0, bfr0);
-      if (DROP) { if (NST1 > 1) load_d1(m0 + D3_BM, 1 / P, bfr1, 1 % P); }
-      else if (D3_AHEAD > 1 && KS1 > 1) load_d1(m0 + D3_BM, 1, bfr1);
-    }
-    if (ht < n_ht2) {
-      // ---- GEMM2: dW_j[h, gene] += sum_row d[row, h] G_j[row, gene] ----
-      bf16x8 bf[2][3];
-      auto load_2 = [&](int st, bf16x8 (&b)[3]) {                    // step = k-step * P + head
-        const int ks = st / P, j = st % P;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          b[pl] = lds_tr8<ROWB>(Gl + (size_t)(j * 3 + pl) * GPLANE + g2b + 16 * ks * ROWB);
-      };
-      load_2(0, bf[0]);
-#pragma unroll
-      for (int st = 0; st < KS2 * P; ++st) {
-        if (st + 1 < KS2 * P) load_2(st + 1, bf[(st + 1) & 1]);
-        if (DROP) {
-          if (st + 2 < NST2) {
-            load_a2((st + 2) / P, a2[(st + 2) % 3], (st + 2) % P);
-            d3_pin_loads();
-          }
-        } else if (st % P == 0 && st / P + D3_AHEAD < KS2) {
-          load_a2(st / P + D3_AHEAD, a2[(st / P + D3_AHEAD) % D3_NB]);
-          d3_pin_loads();
-        }
-        const int ks = st / P, j = st % P;
-#pragma unroll
-        for (int a = 2; a >= 0; --a)
-#pragma unroll
-          for (int b = 2; b >= 0; --b)
-            accW[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[DROP ? st % 3 : ks % D3_NB][a],
-                                                              bf[st & 1][b], accW[j], 0, 0, 0);
-      }
-    }
-    lds_barrier();
-  }
-
-  if (!TRAIN) return;
-  // ---- dW / db of the strip ----
-  if (KSPLIT) {
-    // the two waves of an h tile hold partial sums over the two row halves: waves 4-7 park
-    // theirs in LDS (the weights are no longer needed), waves 0-3 add and write
-    float* park = reinterpret_cast<float*>(smem) + (size_t)ht * P * 16 * 64;
-    if (hi2 == 1 && ht < n_ht2) {
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) park[(j * 16 + i) * 64 + lane] = accW[j][i];
-    }
-    __syncthreads();
-    if (hi2 == 0 && ht < n_ht2) {
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) accW[j][i] += park[(j * 16 + i) * 64 + lane];
-    }
-  }
-  if (ht < n_ht2 && (!KSPLIT || hi2 == 0)) {
-    const int c = c0 + (KSPLIT ? 0 : 32 * hi2) + li;
-    if (c < F) {
-      const size_t gs_out = hp.gene_stride ? hp.gene_stride : 1;
-      const size_t rp_out = hp.row_pitch ? hp.row_pitch : F;
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int h = 32 * ht + (i & 3) + 8 * (i >> 2) + 4 * kh;
-          if (h < H) hp.dW[j][(size_t)h * rp_out + c * gs_out] = accW[j][i];
-          else if (h == H) hp.db[j][c * gs_out] = accW[j][i];
-        }
-    }
-  }
+  constexpr bool IDX = false;
+  const int64_t* const trows = nullptr;
+#include "decoder_head3_body.inc"
+}
+// the uint16 targets through a row index (no head dropout, the four count likelihoods)
+template <int KIND, int KS1, bool TRAIN>
+__global__ __launch_bounds__(D3_THREADS) void decoder_head3_rows_kernel(
+    const uint16_t* __restrict__ dA, const uint16_t* __restrict__ dT, int R, int Rpad, int H,
+    HeadParams hp, int F, Targets tg, int B, const float* __restrict__ gw, int inline_lgamma,
+    float* __restrict__ ll_part, float* __restrict__ dd_part,
+    const int64_t* __restrict__ trows) {
+  constexpr bool U16 = true, DROP = false, IDX = true;
+  constexpr int CP = 0;
+  const uint32_t* const drop_bits = nullptr;
+  const float inv_keep = 1.f;
+  const CpRows cp = CpRows();
+#include "decoder_head3_body.inc"
 }
 
 
@@ -963,6 +390,8 @@ __device__ unsigned long long d4_prof[12 * 8];
 // step) for the decoder widths only this kernel takes -- odd ones and everything beyond 126: the
 // producers' GEMM1 + likelihood + row sums; the gradient planes are not formed (nothing reads G:
 // the compiler drops its arithmetic), the consumers only add up the row sums.
+// IDX (decoder_head4_rows_kernel): the targets through the row index of a resident uint16 matrix,
+// fetched a tile ahead of the target prefetch that uses it (as in decoder_head3_kernel).
 template <int KIND, int KS1, bool U16, int NPW, int BN_ = 0, bool DBP = false,
           int G1 = (NPW == 4 ? 1 : D4_G1_EIGHT), int TERMS = 9, bool FWD = false>
 __global__ __launch_bounds__(d4_threads(NPW)) void decoder_head4_kernel(
@@ -970,636 +399,20 @@ __global__ __launch_bounds__(d4_threads(NPW)) void decoder_head4_kernel(
     HeadParams hp, int F, Targets tg, int B, const float* __restrict__ gw, int inline_lgamma,
     float* __restrict__ ll_part, float* __restrict__ dd_part, int dd_atomic, int rg_tiles,
     float* __restrict__ rg_slab) {
-  using Traits = LikelihoodTraits<KIND>;
-  constexpr int P = Traits::P;
-  constexpr int NT = d4_threads(NPW);
-  constexpr int BN = BN_ ? BN_ : d3_bn(P), ROWB = 2 * BN + 16;
-  constexpr int NT2 = DBP ? KS1 - 1 : KS1;  // 32-wide h tiles of GEMM2
-  constexpr int NHT = (NT2 + 3) / 4;        // h tiles of a consumer wave
-  static_assert(!DBP || (NPW == 4 && KS1 >= 2), "DBP: four producers");
-  constexpr int DF = KS1 < 4 ? KS1 : 4;     // fragment slots of d a producer holds
-  constexpr int GPLANE = D4_BM * ROWB;      // bytes of one [32 rows][BN genes] plane of G
-  constexpr int GBUF = P * 3 * GPLANE;      // one tile's G: [P][3][32][BN + 8] bf16
-  constexpr int NGP = NPW / 2;              // producer waves side by side over the strip's genes
-  constexpr int NSB = BN / (16 * NGP);      // 16-gene blocks of a producer wave
-  static_assert(NSB >= 1 && NSB * 16 * NGP == BN, "producer waves tile the strip");
-  constexpr int NE = 4 * NSB;               // elements of a producer lane
-  constexpr int KS3 = BN / 16;              // 16-gene k-steps of GEMM3 per head
-  constexpr int NGT = BN / 32;              // 32-gene tiles of GEMM2
-  constexpr int LLN = NGP * 4 * D4_BM;      // row-sum partials of a tile: [gene group][q][row]
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int HP1 = d3_hp1(H);
-  const int WPLANE = HP1 * ROWB;                    // bytes of one [HP1][BN] plane of W
-  char* Wl = smem;                                  // [P][3][HP1][BN + 8] bf16
-  char* Gl = smem + (size_t)P * 3 * WPLANE;         // [2][P][3][32][BN + 8] bf16
-  float* llbuf = reinterpret_cast<float*>(Gl + 2 * GBUF);   // [2][LLN]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = lane >> 4, i16 = lane & 15, li = lane & 31, kh = lane >> 5;
-  const int c0 = blockIdx.x * BN;
-  // (probe build only: ablation flags travel in the upper bits of inline_lgamma -- 1 consumers
-  //  idle, 2 producers idle, 4 no non-zero walk, 8 no dd stores; tools/d4_probe.sh, d4_prof.py)
-  const int dbg = D4_PROF ? inline_lgamma >> 8 : 0;
-  inline_lgamma &= 0xFF;
-
-  // ---- LDS: zero fill, then the strip's weights and biases cut into planes (as above) ----
-  constexpr int HSTEP = NT / BN;
-  constexpr int NV = (32 * KS1 + HSTEP - 1) / HSTEP;    // rows 0 .. H < 32 KS1 of a thread
-  {
-    const int g = tid & (BN - 1), h0 = tid / BN;
-    const bool col_ok = c0 + g < F;
-    const int gc = min(c0 + g, F - 1);
-    float v[P][NV];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      const float* wj = hp.W[j] + gc;
-      const float* bj = hp.b[j] + gc;
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int h = min(h0 + u * HSTEP, H);
-        const float* src = h < H ? wj + (size_t)h * F : bj;
-        v[j][u] = *src;
-      }
-    }
-    {
-      const int n16 = (int)(((size_t)P * 3 * WPLANE + 2 * GBUF + 2 * LLN * 4) / 16);
-      u32x4* z = reinterpret_cast<u32x4*>(smem);
-      for (int i = tid; i < n16; i += NT) z[i] = u32x4{0u, 0u, 0u, 0u};
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int h = h0 + u * HSTEP;
-        if (h <= H) {
-          unsigned b1, b2, b3;
-          split3_rn(col_ok ? v[j][u] : 0.f, b1, b2, b3);
-          char* dst = Wl + (size_t)(j * 3) * WPLANE + h * ROWB + 2 * g;
-          *reinterpret_cast<uint16_t*>(dst) = (uint16_t)(b1 >> 16);
-          *reinterpret_cast<uint16_t*>(dst + WPLANE) = (uint16_t)(b2 >> 16);
-          *reinterpret_cast<uint16_t*>(dst + 2 * WPLANE) = (uint16_t)(b3 >> 16);
-        }
-      }
-  }
-  __syncthreads();
-
-  // (strip x ROW GROUP: workgroup (x, y) takes the 32-row tiles y * rg_tiles .. of strip x, so
-  //  that the launch fills whole rounds of the CUs whatever the gene count -- d4_row_groups.  ll
-  //  and dd are per row; the strip's dW / db of row group 0 go to the gradient buffers, those of
-  //  the groups behind it to rg_slab [group - 1][P][H + 1][F], summed by d4_rg_combine_kernel)
-  const int tile0 = blockIdx.y * rg_tiles;
-  const int n_tiles = min((R + D4_BM - 1) / D4_BM, tile0 + rg_tiles);
-  const int mfirst = tile0 * D4_BM;
-  auto grad_row = [&](int j, int h) -> float* {       // dW_j[h, :] (h < H) or db_j (h == H)
-    if (blockIdx.y == 0) return h < H ? hp.dW[j] + (size_t)h * F : hp.db[j];
-    return rg_slab + (((size_t)(blockIdx.y - 1) * P + j) * (H + 1) + h) * F;
-  };
-  const int KP = d3_kp(H), ksp = KP / 32;   // padded width of the planes of d, in elements / steps
-  const size_t dplane = (size_t)Rpad * KP;
-  const int nb16 = Rpad / 16;
-
-  if (w < NPW) {
-    // =========================== producers: GEMM1 + likelihood + G ===========================
-    // (their GEMM1 + likelihood chain is the longer of the two; measured: which producers win the
-    //  arbitration changes who waits at the barrier, not the tile time)
-    __builtin_amdgcn_s_setprio(D4_PRIO_PRODUCER);
-    const int gp = w % NGP, rq = w / NGP;     // genes 16 NSB gp .., rows 16 rq .. of the tile
-    const int gbase = 16 * NSB * gp;
-    const int trw = (8 * q + (i16 >> 2)) * ROWB + 2 * (gbase + 4 * (i16 & 3));        // W, GEMM1
-    const int gst = (16 * rq + i16) * ROWB + 2 * (gbase + 4 * q);                     // G store
-    struct TileIn { f32x4m t[NSB]; float up0; };
-    auto load_t = [&](int m0) {
-      TileIn in;
-      const int row = m0 + 16 * rq + i16;
-      const bool rok = row < R;
-      in.up0 = (rok && !FWD) ? gw[row] : 0.f;
-      const int rc = rok ? row : R - 1;
-      const int cell = R == B ? rc : rc % B;
-      const size_t trow = (size_t)cell * tg.ld;
-#pragma unroll
-      for (int sb = 0; sb < NSB; ++sb) {
-        const int c = c0 + gbase + 16 * sb + 4 * q;
-        f32x4m v = {0.f, 0.f, 0.f, 0.f};
-        if (U16) {        // pitch % 8 == 0, padding columns zero: one 8-byte load
-          const uint16_t* tp = static_cast<const uint16_t*>(tg.p) + trow + c;
-          const u32x2 u = *reinterpret_cast<const u32x2*>(tp);
-          v.x = __uint_as_float(u.x); v.y = __uint_as_float(u.y);
-        } else {
-          const float* tp = static_cast<const float*>(tg.p) + trow + c;
-          if (c + 3 < F) {
-            const f32x4u u = *reinterpret_cast<const f32x4u*>(tp);
-            v.x = u.x; v.y = u.y; v.z = u.z; v.w = u.w;
-          } else {
-            v.x = (c < F) ? tp[0] : 0.f;
-            v.y = (c + 1 < F) ? tp[1] : 0.f;
-            v.z = (c + 2 < F) ? tp[2] : 0.f;
-          }
-        }
-        in.t[sb] = v;
-      }
-      return in;
-    };
-    // d fragments of GEMM1 (B[k = h][n = row]): 3 planes per k-step, one contiguous KiB each; a
-    // whole tile's worth is requested at once, behind the previous tile's GEMM1, and lands under
-    // that tile's likelihood
-    bf16x8 dfr[DF][3];
-    auto load_dk = [&](int m0, int ks, bf16x8 (&dst)[3]) {
-      const uint16_t* dbase = dA + ((size_t)(m0 / 16 + rq) * ksp + ks) * 512 + lane * 8;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) dst[pl] = global_b128(dbase + pl * dplane);
-    };
-    auto load_d = [&](int m0) {       // the first DF steps of a tile
-#pragma unroll
-      for (int ks = 0; ks < DF; ++ks) load_dk(m0, ks, dfr[ks]);
-    };
-    // GEMM1 of a tile from the fragments of d in dfr: pre_j^T[gene, row] on the accumulators
-    f32x4m acc1[P][NSB];
-    auto gemm1 = [&](int mt) {      // (mt: the tile's first row -- steps beyond DF are requested here)
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) acc1[j][sb] = f32x4m{0.f, 0.f, 0.f, 0.f};
-      bf16x8 afr[2][P][NSB][3];
-      auto load_w = [&](int ks, bf16x8 (&dst)[P][NSB][3]) {
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-#pragma unroll
-          for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-              dst[j][sb][pl] = lds_tr8<ROWB>(Wl + (size_t)(j * 3 + pl) * WPLANE + trw + 32 * sb +
-                                             32 * ks * ROWB);
-      };
-      load_w(0, afr[0]);
-#pragma unroll
-      for (int ks = 0; ks < KS1; ++ks) {
-        if (ks + 1 < KS1) load_w(ks + 1, afr[(ks + 1) & 1]);
-        // small terms first; the accumulators (head x gene block) are independent chains
-#pragma unroll
-        for (int a = 2; a >= 0; --a)
-#pragma unroll
-          for (int b = 2; b >= 0; --b)
-#pragma unroll
-            for (int j = 0; j < P; ++j)
-#pragma unroll
-              for (int sb = 0; sb < NSB; ++sb)
-                if (TERMS == 9 || a + b < 3) acc1[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    afr[ks & 1][j][sb][a], dfr[ks % DF][b], acc1[j][sb], 0, 0, 0);
-        if (ks + DF < KS1) {        // this step's slot is free: step ks + DF of the same tile
-          load_dk(mt, ks + DF, dfr[ks % DF]);
-          d3_pin_loads();
-        }
-      }
-    };
-    // (g1last) the barrier sits between GEMM1 of a tile and its likelihood: when it releases, the
-    // producers are in their VALU stretch and the consumers' GEMM2 finds the matrix pipe free;
-    // the producers' GEMM1 of the NEXT tile runs at the end of the iteration, under the
-    // consumers' stores (or atomic adds) of dd, which issue no matrix instructions.
-    float dbacc[P][NE];                 // (DBP) this lane's part of db_j: its genes, its rows
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-      for (int e = 0; e < NE; ++e) dbacc[j][e] = 0.f;
-    TileIn nxt = load_t(mfirst);
-    load_d(mfirst);
-    const bool g1last = G1 == 1 || (G1 == 2 && w >= NPW / 2);    // (wave-uniform)
-    if (g1last) {
-      gemm1(mfirst);
-      load_d(min(mfirst + D4_BM, Rpad - D4_BM));
-      d3_pin_loads();
-    }
-    D4_PROF_BEGIN;
-    for (int tile = tile0; tile < n_tiles; ++tile) {
-      const int m0 = tile * D4_BM;
-      if (dbg & 2) { lds_barrier(); continue; }
-      const TileIn cur = nxt;
-      const float up = cur.up0;
-      char* Gb = Gl + ((tile - tile0) & 1) * GBUF;
-      float* lb = llbuf + ((tile - tile0) & 1) * LLN;
-      if (!g1last) gemm1(m0);
-      {
-        // the next tile's targets (and, GEMM1 first, its fragments of d): under the likelihood.
-        // Unconditional (the last tile requests a valid tile again): under a branch the compiler
-        // waits for the loads where the arms meet
-        nxt = load_t(min(m0 + D4_BM, Rpad - D4_BM));
-        if (!g1last) load_d(min(m0 + D4_BM, Rpad - D4_BM));
-        d3_pin_loads();
-      }
-      // ---- likelihood of this lane's NSB x 4 elements: row 16 rq + i16, genes
-      //      16 NSB gp + 16 sb + 4 q + e ----
-      float G[P][NE], tval[NE];
-      float lsum = 0.f;
-      unsigned nz = 0;
-#pragma unroll
-      for (int sb = 0; sb < NSB; ++sb) {
-        if (U16) {
-          const unsigned v0 = __float_as_uint(cur.t[sb][0]), v1 = __float_as_uint(cur.t[sb][1]);
-          tval[4 * sb] = (float)(v0 & 0xFFFFu); tval[4 * sb + 1] = (float)(v0 >> 16);
-          tval[4 * sb + 2] = (float)(v1 & 0xFFFFu); tval[4 * sb + 3] = (float)(v1 >> 16);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) tval[4 * sb + e] = cur.t[sb][e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a[P], g[P], lp, r, rgate;
-#pragma unroll
-          for (int j = 0; j < P; ++j) a[j] = acc1[j][sb][e];
-          lik_dense<KIND, true>(tval[4 * sb + e], a, lp, g, r, rgate);
-          const bool ok = c0 + gbase + 16 * sb + 4 * q + e < F;
-          lsum += ok ? lp : 0.f;
-#pragma unroll
-          for (int j = 0; j < P; ++j) G[j][4 * sb + e] = up * g[j];
-          nz |= (ok && tval[4 * sb + e] > 0.f) ? (1u << (4 * sb + e)) : 0u;
-        }
-      }
-      D4_STAMP(1);
-      if constexpr (d4_compact(KS1)) {
-      // ---- t > 0: + lgamma(r+t) - lgamma(r) [- lgamma(1+t)], and the digamma term of dlog r.
-      //      5 % of the elements: instead of a per-lane walk (as many passes as the fullest lane
-      //      holds non-zeros -- 1.6 on average with a fifth of the lanes busy, and the VALU
-      //      instructions of these waves are what the tile time is made of), the wave's non-zeros
-      //      are queued densely -- (t, log r) at position [elements e' < e of all lanes][lanes
-      //      below] from one ballot per element slot -- corrected in ONE pass of full lanes, and
-      //      read back by their owners.  The queue is 512 bytes of LDS of the wave's own (64
-      //      entries: one pass per 64 non-zeros).  (Kept in the wave's corner of the G buffer
-      //      the tile is about to fill, the kernels whose GEMM1 sits at the end of the
-      //      iteration were not repeatable from run to run -- 26-40 of 40 launches differed,
-      //      in sporadic elements whose log r came out of GEMM1 wrong -- although no other
-      //      wave touches that corner between the two barriers; with the queue in LDS of
-      //      its own: 0 of 40.  Not strict aliasing (-fno-strict-aliasing: the same), rarer
-      //      with dd through slabs (0-2 of 30), and gone with the queue in the buffer's LAST
-      //      plane instead of its first.  Not understood; tools/time_head.py TIME_HEAD_STRESS.) ----
-      if ((Traits::HAS_R || inline_lgamma) && !(dbg & 4)) {
-        int pos[NE];
-        int total = 0;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          const unsigned long long bal = __builtin_amdgcn_ballot_w64(((nz >> e) & 1u) != 0u);
-          pos[e] = total + (int)__builtin_amdgcn_mbcnt_hi(
-                               (unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-          total += __builtin_popcountll(bal);
-        }
-        char* qb = reinterpret_cast<char*>(llbuf + 2 * LLN) + w * 512;
-        auto qaddr = [&](int k) { return qb + 8 * k; };
-        for (int q0 = 0; q0 < total; q0 += 64) {
-#pragma unroll
-          for (int e = 0; e < NE; ++e) {
-            const int k = pos[e] - q0;
-            if (((nz >> e) & 1u) && (unsigned)k < 64u) {
-              const float lrv = Traits::HAS_R ? acc1[P - 1][e >> 2][e & 3] : 0.f;
-              *reinterpret_cast<f32x2*>(qaddr(k)) = f32x2{tval[e], lrv};
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-          const bool on = lane < total - q0;
-          f32x2 in = *reinterpret_cast<const f32x2*>(qaddr(lane));
-          const float tt = on ? in.x : 1.f;
-          float corr = 0.f, rd = 0.f;
-          if (Traits::HAS_R) {
-            const float lrv = on ? in.y : 0.f;
-            const float r = __expf(fminf(fmaxf(lrv, -10.f), 10.f));
-            const float rgate = (lrv >= -10.f && lrv <= 10.f) ? 1.f : 0.f;
-            const bool small = tt <= 8.f && (U16 || tt == __builtin_rintf(tt));
-            float A, D;
-            if (__builtin_amdgcn_ballot_w64(!small) == 0)
-              lgamma_digamma_diff_small_wave<true>(r, tt, A, D);
-            else
-              lgamma_digamma_diff_general<true>(r, tt, A, D);
-            corr = A;
-            rd = rgate * r * D;
-          }
-          if (inline_lgamma) corr -= lgamma1p(tt);
-          if (on) *reinterpret_cast<f32x2*>(qaddr(lane)) = f32x2{corr, rd};
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int e = 0; e < NE; ++e) {
-            const int k = pos[e] - q0;
-            if (((nz >> e) & 1u) && (unsigned)k < 64u) {
-              const f32x2 o = *reinterpret_cast<const f32x2*>(qaddr(k));
-              lsum += o.x;
-              if (Traits::HAS_R) G[P - 1][e] = fmaf(up, o.y, G[P - 1][e]);
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-      } else {
-      // ---- t > 0: + lgamma(r+t) - lgamma(r) [- lgamma(1+t)], and the digamma term of dlog r:
-      //      a per-lane walk over the lane's non-zero elements ----
-      if ((Traits::HAS_R || inline_lgamma) && !(dbg & 4)) {
-        float lr[NE];
-        if (Traits::HAS_R) {
-#pragma unroll
-          for (int i = 0; i < NE; ++i) lr[i] = acc1[P - 1][i >> 2][i & 3];
-        }
-        while (__builtin_amdgcn_ballot_w64(nz != 0) != 0) {
-          const bool on = nz != 0;
-          const int idx = on ? __builtin_ctz(nz) : 0;
-          nz &= nz - 1;
-          const IndexMasks3 km = index_masks3(idx);
-          const float tt = select_n(tval, km);
-          float corr = 0.f;
-          if (Traits::HAS_R) {
-            const float lrv = select_n(lr, km);
-            const float r = __expf(fminf(fmaxf(lrv, -10.f), 10.f));
-            const float rgate = (lrv >= -10.f && lrv <= 10.f) ? 1.f : 0.f;
-            const bool small = !on || (tt <= 8.f && tt == __builtin_rintf(tt));
-            float A, D;
-            if (__builtin_amdgcn_ballot_w64(!small) == 0)
-              lgamma_digamma_diff_small_wave<true>(r, on ? tt : 0.f, A, D);
-            else
-              lgamma_digamma_diff_general<true>(r, on ? tt : 1.f, A, D);
-            corr = A;
-            const float delta = on ? up * rgate * r * D : 0.f;
-#pragma unroll
-            for (int e = 0; e < NE; ++e) G[P - 1][e] += (idx == e) ? delta : 0.f;
-          }
-          if (inline_lgamma) corr -= lgamma1p(tt);
-          lsum += on ? corr : 0.f;
-        }
-      }
-      }
-      D4_STAMP(2);
-      if (DBP && !FWD) {
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-#pragma unroll
-          for (int e = 0; e < NE; ++e) dbacc[j][e] += G[j][e];
-      }
-      // ---- this lane's part of the row sum -> lb[gp][q][row]: the consumers add the parts ----
-      lb[(gp * 4 + q) * D4_BM + 16 * rq + i16] = lsum;
-      // ---- G_j -> three bf16 planes, row-major [row][gene], 8 bytes (4 genes) per store ----
-      if constexpr (!FWD)
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) {
-          unsigned p1[2], p2[2], p3[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e)
-            split3_rn_pair(G[j][4 * sb + 2 * e], G[j][4 * sb + 2 * e + 1], p1[e], p2[e], p3[e]);
-          char* dst = Gb + (size_t)(j * 3) * GPLANE + gst + 32 * sb;
-          *reinterpret_cast<u32x2*>(dst) = u32x2{p1[0], p1[1]};
-          *reinterpret_cast<u32x2*>(dst + GPLANE) = u32x2{p2[0], p2[1]};
-          *reinterpret_cast<u32x2*>(dst + 2 * GPLANE) = u32x2{p3[0], p3[1]};
-        }
-      D4_STAMP(3);
-      // GEMM1 of the next tile (the last iteration: a valid tile again, unused), then the request
-      // for the fragments of the tile after it
-      if (g1last) {
-        gemm1(min(m0 + D4_BM, Rpad - D4_BM));
-        load_d(min(m0 + 2 * D4_BM, Rpad - D4_BM));
-        d3_pin_loads();
-      }
-      D4_STAMP(0);
-      lds_barrier();
-      D4_STAMP(4);
-    }
-    lds_barrier();     // (the consumers' pass over the last tile)
-    D4_PROF_END;
-    if (DBP && !FWD) {
-      // db_j[gene] = sum over the rows: over the 16 lanes of a q group (the tile's rows of this
-      // wave), then over the row blocks rq through LDS (the G tiles are free now), fixed order
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          float v = dbacc[j][e];
-#pragma unroll
-          for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, WAVE);
-          dbacc[j][e] = v;
-        }
-      float* park = reinterpret_cast<float*>(Gl);        // [gp][j][e][q]
-      if (rq == 1 && i16 == 0) {
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-#pragma unroll
-          for (int e = 0; e < NE; ++e) park[((gp * P + j) * NE + e) * 4 + q] = dbacc[j][e];
-      }
-      lds_barrier();     // (every wave of the workgroup: the consumers pass it before their dW)
-      if (rq == 0 && i16 == 0) {
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-#pragma unroll
-          for (int e = 0; e < NE; ++e) {
-            const int c = c0 + gbase + 16 * (e >> 2) + 4 * q + (e & 3);
-            if (c < F) grad_row(j, H)[c] = dbacc[j][e] + park[((gp * P + j) * NE + e) * 4 + q];
-          }
-      }
-    }
-    return;
-  }
-
-  // =========================== consumers: GEMM3 (dd) and GEMM2 (dW) ===========================
-  __builtin_amdgcn_s_setprio(D4_PRIO_CONSUMER);
-  if constexpr (FWD) {
-    // forward only: the strip's per-row log-likelihood, the producers' parts in a fixed order
-    lds_barrier();       // (the producers' first tile)
-    for (int tile = tile0; tile < n_tiles; ++tile) {
-      const int m0 = tile * D4_BM;
-      const float* lb = llbuf + ((tile - tile0) & 1) * LLN;
-      if (w == NPW && lane < D4_BM && m0 + lane < R) {
-        float sm = 0.f;
-#pragma unroll
-        for (int u = 0; u < NGP * 4; ++u) sm += lb[u * D4_BM + lane];
-        ll_part[(size_t)blockIdx.x * R + m0 + lane] = sm;
-      }
-      lds_barrier();
-    }
-    return;
-  }
-  const int ht = w - NPW;                         // h tile of this wave
-  // (dd_atomic) the accumulator copy of the XCD this workgroup actually runs on: its adds are
-  // then performed in that XCD's own L2, the only L2 that ever holds lines of that copy --
-  // correct whatever the dispatcher's block -> XCD placement is
-  unsigned xcc = 0;
-  if (dd_atomic) {
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7u;
-    // (probe build, timing only -- the sums are wrong: the workgroups of an XCD spread over the
-    //  eight copies, a quarter of the adds per line at a time)
-    if (dbg & 16) xcc = (blockIdx.x >> 3) & 7u;
-  }
-  const int n_ht3 = (H + 31) / 32, n_ht2 = DBP ? H / 32 : (H + 1 + 31) / 32;
-  // this wave's h tiles: ht, ht + 4, ... (NHT of them; one for H <= 126)
-  const int g3a = li * ROWB + 16 * kh;                                               // G, GEMM3
-  const int g3b = (32 * ht + li) * ROWB + 16 * kh;                                   // W, GEMM3
-  const int g2b = (8 * (q >> 1) + (i16 >> 2)) * ROWB + 2 * (16 * (q & 1) + 4 * (i16 & 3));  // G, GEMM2
-  f32x16 accW[NHT][P][NGT];                 // dW tiles (h tile x gene tile) of every head
-#pragma unroll
-  for (int t = 0; t < NHT; ++t)
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-      for (int gt = 0; gt < NGT; ++gt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) accW[t][j][gt][i] = 0.f;
-  // GEMM2's d fragments (A[i = h][k = row]): one contiguous KiB per plane and 16-row k-step; the
-  // two k-steps of (row tile, h tile) are requested while the wave works on the pair before
-  constexpr int NA2 = NHT > 1 ? 2 : 1;
-  bf16x8 a2[NA2][2][3];
-  auto load_a2k = [&](int m0, int t, int ks, bf16x8 (&dst)[3]) {
-    // (h tile clamped to the planes' last: a wave without a tile t requests a valid one, unused
-    //  -- no branch around the loads, at whose end the compiler would wait for them)
-    const int htt = min(ht + 4 * t, ksp - 1);
-    const uint16_t* tb = dT + ((size_t)htt * nb16 + m0 / 16 + ks) * 512 + lane * 8;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) dst[pl] = global_b128(tb + pl * dplane);
-  };
-  auto load_a2 = [&](int m0, int t, bf16x8 (&dst)[2][3]) {
-    load_a2k(m0, t, 0, dst[0]);
-    load_a2k(m0, t, 1, dst[1]);
-  };
-  // (across the barrier -- and across GEMM3, where the wave's register need peaks -- only the
-  //  first k-step of the next row tile travels; the second is requested when its GEMM2 starts,
-  //  half a GEMM2 ahead of its use)
-  if (ht < n_ht2) load_a2k(mfirst, 0, 0, a2[0][0]);
-  lds_barrier();       // (the producers' first tile)
-  D4_PROF_BEGIN;
-  for (int tile = tile0; tile < n_tiles; ++tile) {
-    const int m0 = tile * D4_BM;
-    const char* Gb = Gl + ((tile - tile0) & 1) * GBUF;
-    const float* lb = llbuf + ((tile - tile0) & 1) * LLN;
-    // per-row log-likelihood of the strip: the producers' parts summed in a fixed order
-    if (w == NPW && lane < D4_BM && m0 + lane < R) {
-      float sm = 0.f;
-#pragma unroll
-      for (int u = 0; u < NGP * 4; ++u) sm += lb[u * D4_BM + lane];
-      ll_part[(size_t)blockIdx.x * R + m0 + lane] = sm;
-    }
-    D4_STAMP(0);
-    // (GEMM2 first: GEMM3's stores -- or atomic adds -- of this tile's part of dd then sit
-    //  right before the barrier and drain under the wait and the next tile's GEMM2)
-#pragma unroll
-    for (int t = 0; t < NHT; ++t) {
-      if (ht + 4 * t < n_ht2 && !(dbg & 1)) {
-        // ---- GEMM2: dW_j[h, gene] += sum_row d[row, h] G_j[row, gene] ----
-        bf16x8 (&a2t)[2][3] = a2[t % NA2];
-        if (t == 0) {
-          load_a2k(m0, 0, 1, a2[0][1]);
-          d3_pin_loads();
-        }
-        if (t + 1 < NHT) {
-          load_a2(m0, t + 1, a2[(t + 1) % NA2]);
-          d3_pin_loads();
-        }
-        constexpr int NST = 2 * P * NGT;             // step = (k-step * P + head) * NGT + gene tile
-        bf16x8 bf[2][3];
-        auto load_2 = [&](int st, bf16x8 (&b)[3]) {
-          const int gt = st % NGT, j = (st / NGT) % P, ks = st / (NGT * P);
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl)
-            b[pl] = lds_tr8<ROWB>(Gb + (size_t)(j * 3 + pl) * GPLANE + g2b + 64 * gt +
-                                  16 * ks * ROWB);
-        };
-        load_2(0, bf[0]);
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-          if (st + 1 < NST) load_2(st + 1, bf[(st + 1) & 1]);
-          const int gt = st % NGT, j = (st / NGT) % P, ks = st / (NGT * P);
-#pragma unroll
-          for (int a = 2; a >= 0; --a)
-#pragma unroll
-            for (int b = 2; b >= 0; --b)
-              if (TERMS == 9 || a + b < 3) accW[t][j][gt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2t[ks][a], bf[st & 1][b],
-                                                                       accW[t][j][gt], 0, 0, 0);
-        }
-      }
-    }
-    if (ht < n_ht2 && !(dbg & 1)) {
-      // the next row tile's fragments of this wave's first h tile (the last tile: its own
-      // again), in flight over the barrier
-      load_a2k(min(m0 + D4_BM, Rpad - D4_BM), 0, 0, a2[0][0]);
-      d3_pin_loads();
-    }
-    D4_STAMP(2);
-#pragma unroll
-    for (int t = 0; t < NHT; ++t) {
-      if (ht + 4 * t < n_ht3 && !(dbg & 1)) {
-        // ---- GEMM3: dd^T[h, row] = sum_j sum_gene W_j[h, gene] G_j[row, gene] ----
-        const int htt = ht + 4 * t;
-        f32x16 acc3;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc3[i] = 0.f;
-        bf16x8 af[2][3], bf[2][3];
-        auto load_3 = [&](int st, bf16x8 (&a)[3], bf16x8 (&b)[3]) {   // step = head * KS3 + k-step
-          const int j = st / KS3, ks = st % KS3;
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            a[pl] = lds_b128(Gb + (size_t)(j * 3 + pl) * GPLANE + g3a + 32 * ks);
-            b[pl] = lds_b128(Wl + (size_t)(j * 3 + pl) * WPLANE + g3b + 128 * t * ROWB + 32 * ks);
-          }
-        };
-        load_3(0, af[0], bf[0]);
-#pragma unroll
-        for (int st = 0; st < KS3 * P; ++st) {
-          if (st + 1 < KS3 * P) load_3(st + 1, af[(st + 1) & 1], bf[(st + 1) & 1]);
-#pragma unroll
-          for (int a = 2; a >= 0; --a)
-#pragma unroll
-            for (int b = 2; b >= 0; --b)
-              if (TERMS == 9 || a + b < 3) acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[st & 1][b], af[st & 1][a], acc3,
-                                                             0, 0, 0);
-        }
-        D4_STAMP(1);
-        const int row = (dbg & 8) ? R : m0 + li;
-        if (dd_atomic) {
-          // no-return fp32 adds into this XCD's [H][R] accumulator (h-major: the 32 lanes of a
-          // half wave add to 128 contiguous bytes); dd_reduce_xcd_kernel sums the eight copies
-          if (row < R) {
-            typedef __attribute__((address_space(1))) float gfloat;
-            float* base = dd_part + ((size_t)xcc * H + 32 * htt + 4 * kh) * R + row;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (32 * htt + 8 * c + 4 * kh + e < H)
-                  __builtin_amdgcn_global_atomic_fadd_f32(
-                      (gfloat*)(base + (size_t)(8 * c + e) * R), acc3[4 * c + e]);
-          }
-        } else if (row < R) {
-          // slab [strip][H / 4][R][4] (see decoder_head3_kernel): one 16-byte store per h quad
-          const int HQ = (H + 3) >> 2;
-          f32x4m* dst = reinterpret_cast<f32x4m*>(dd_part) +
-                        ((size_t)blockIdx.x * HQ + 8 * htt + kh) * R + row;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            if (4 * (8 * htt + 2 * c + kh) < H)
-              __builtin_nontemporal_store(
-                  f32x4m{acc3[4 * c], acc3[4 * c + 1], acc3[4 * c + 2], acc3[4 * c + 3]},
-                  dst + (size_t)2 * c * R);
-          }
-        }
-      }
-    }
-    D4_STAMP(3);
-    lds_barrier();
-    D4_STAMP(4);
-  }
-  D4_PROF_END;
-  if (DBP) lds_barrier();     // (the producers' exchange of their db parts)
-  // ---- dW / db of the strip ----
-#pragma unroll
-  for (int t = 0; t < NHT; ++t) {
-    const int htt = ht + 4 * t;
-    if (htt < n_ht2) {
-#pragma unroll
-      for (int gt = 0; gt < NGT; ++gt) {
-        const int c = c0 + 32 * gt + li;
-        if (c < F) {
-#pragma unroll
-          for (int j = 0; j < P; ++j)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-              const int h = 32 * htt + (i & 3) + 8 * (i >> 2) + 4 * kh;
-              if (h <= H) grad_row(j, h)[c] = accW[t][j][gt][i];
-            }
-        }
-      }
-    }
-  }
+  constexpr bool IDX = false;
+  const int64_t* const trows = nullptr;
+#include "decoder_head4_body.inc"
+}
+// the uint16 targets through a row index (all nine terms)
+template <int KIND, int KS1, int NPW, int BN_, bool DBP, int G1, bool FWD>
+__global__ __launch_bounds__(d4_threads(NPW)) void decoder_head4_rows_kernel(
+    const uint16_t* __restrict__ dA, const uint16_t* __restrict__ dT, int R, int Rpad, int H,
+    HeadParams hp, int F, Targets tg, int B, const float* __restrict__ gw, int inline_lgamma,
+    float* __restrict__ ll_part, float* __restrict__ dd_part, int dd_atomic, int rg_tiles,
+    float* __restrict__ rg_slab, const int64_t* __restrict__ trows) {
+  constexpr bool U16 = true, IDX = true;
+  constexpr int TERMS = 9;
+#include "decoder_head4_body.inc"
 }
 
 #if D4_PROF
@@ -1759,6 +572,7 @@ struct D4Launch {
   Targets t; int B; const float* gw; int inline_lgamma; float* ll_part; float* dd_part;
   int dd_atomic; int strips; size_t lds; int terms; int row_groups; float* rg_slab;
   bool fwd = false;      // the forward half alone (decoder_head4_kernel<..., FWD = true>)
+  const int64_t* trows = nullptr;   // the uint16 targets through a row index (..._rows_kernel)
 };
 template <int KIND, int KS1, int NPW, int BN_, bool DBP = false, int TERMS = 9>
 static int d4_launch_one(const D4Launch& a) {
@@ -1771,6 +585,27 @@ static int d4_launch_one(const D4Launch& a) {
   const int tiles = (a.rows + D4_BM - 1) / D4_BM;
   const int rg_tiles = (tiles + a.row_groups - 1) / a.row_groups;
   const int groups = (tiles + rg_tiles - 1) / rg_tiles;     // (no empty group)
+  if (a.trows) {
+    if constexpr (TERMS == 9) {
+      if (!a.t.u16 || a.terms != 9) {
+        set_error("decoder_head4_kernel: a row index goes with uint16 targets and nine terms");
+        return -1;
+      }
+      auto rfn = a.fwd ? decoder_head4_rows_kernel<KIND, KS1, NPW, BN_, DBP, G1, true>
+                       : decoder_head4_rows_kernel<KIND, KS1, NPW, BN_, DBP, G1, false>;
+      SCVAE_HIP(max_dynamic_lds(reinterpret_cast<const void*>(rfn), (int)a.lds));
+      hipLaunchKernelGGL(rfn, dim3(a.strips, groups), dim3(d4_threads(NPW)), a.lds, a.s, a.dA,
+                         a.dT, a.rows, a.Rpad, a.H, a.hp, a.F, a.t, a.B, a.gw, a.inline_lgamma,
+                         a.ll_part, a.dd_part, a.fwd ? 0 : a.dd_atomic, rg_tiles,
+                         a.fwd ? nullptr : a.rg_slab, a.trows);
+      if (!a.fwd && groups > 1) {
+        constexpr int P = likelihood_heads(KIND);
+        hipLaunchKernelGGL(d4_rg_combine_kernel, dim3((a.F + 1023) / 1024, P * (a.H + 1)),
+                           dim3(256), 0, a.s, a.hp, P, a.H, a.F, a.rg_slab, groups - 1);
+      }
+      return 0;
+    }
+  }
   if constexpr (TERMS == 9) {
     if (a.fwd) {
       auto ffn = a.t.u16 ? decoder_head4_kernel<KIND, KS1, true, NPW, BN_, DBP, G1, 9, true>
@@ -1846,8 +681,10 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
                           HeadParams hp, int F, Targets t, int B, const float* gw,
                           int inline_lgamma, float* ll_part, float* dd_part, float* planes,
                           const HeadDropout* drop, int cp_pass, const CpRows* cp, int dd_mode,
-                          float* rg_slab) {
+                          float* rg_slab, const int64_t* t_rows) {
   const int P = likelihood_heads(kind);
+  // (a row index: uint16 targets of the four count likelihoods, plain launches)
+  SCVAE_ARG(!t_rows || (t.u16 && kind <= LK_ZINB && !drop && cp_pass == 0 && !(dd_mode & 6)));
   // (head4 alone: beyond the all-in-one-phase kernel's LDS budget; forward-only calls also the
   //  widths and head counts that kernel's forward instantiation does not take -- odd widths, three
   //  heads: decoder_fused_forward sends it exactly those)
@@ -1908,6 +745,20 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
                        t, B, gw, inline_lgamma, ll_part, dd_part, bits, inv_keep, cpr);           \
   } while (0)
 #define SCVAE_D3K(K_, KS_, T_, D_) SCVAE_D3KC(K_, KS_, T_, D_, 0)
+#define SCVAE_D3RK(K_, KS_, T_)                                                                   \
+  do {                                                                                            \
+    auto kfn = decoder_head3_rows_kernel<K_, KS_, T_>;                                            \
+    SCVAE_HIP(max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)lds));                     \
+    hipLaunchKernelGGL(kfn, dim3(strips), dim3(D3_THREADS), lds, s, dA, dT, rows, Rpad, H, hp, F, \
+                       t, B, gw, inline_lgamma, ll_part, dd_part, t_rows);                        \
+  } while (0)
+#define SCVAE_D3R(K_, T_)                                                                         \
+  switch (ks1) {                                                                                  \
+    case 1: SCVAE_D3RK(K_, 1, T_); break;                                                         \
+    case 2: SCVAE_D3RK(K_, 2, T_); break;                                                         \
+    case 3: SCVAE_D3RK(K_, 3, T_); break;                                                         \
+    default: SCVAE_D3RK(K_, 4, T_); break;                                                        \
+  }
 #define SCVAE_D3C(T_, C_)                                                                         \
   switch (ks1) {                                                                                  \
     case 1: SCVAE_D3KC(LK_CPOISSON, 1, T_, false, C_); break;                                     \
@@ -1944,6 +795,7 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
                (dd_mode & 1) ? 1 : 0, (F + c.bn - 1) / c.bn, c.lds, (dd_mode & 2) ? 6 : 9, 1,
                rg_slab};
     a.fwd = !train;
+    a.trows = t_rows;
     if (a.fwd) { a.dd_atomic = 0; a.terms = 9; }
     // (no slab from the caller: one group -- the stand-alone forward-only / probe entries; the
     //  forward half leaves no dW and needs none)
@@ -1960,6 +812,20 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
       default: set_error("decoder_head4_kernel: likelihood kind %d", kind); return -1;
     }
     if (rc) return rc;
+  } else if (t_rows && train) {
+    switch (kind) {
+      case LK_POISSON: SCVAE_D3R(LK_POISSON, true); break;
+      case LK_NB: SCVAE_D3R(LK_NB, true); break;
+      case LK_ZIP: SCVAE_D3R(LK_ZIP, true); break;
+      default: SCVAE_D3R(LK_ZINB, true); break;
+    }
+  } else if (t_rows) {
+    switch (kind) {
+      case LK_POISSON: SCVAE_D3R(LK_POISSON, false); break;
+      case LK_NB: SCVAE_D3R(LK_NB, false); break;
+      case LK_ZIP: SCVAE_D3R(LK_ZIP, false); break;
+      default: set_error("decoder_head3_kernel (forward): likelihood kind %d", kind); return -1;
+    }
   } else if (train) {
     switch (kind) {
       case LK_POISSON: SCVAE_D3(LK_POISSON, true, false); break;
@@ -1981,6 +847,8 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
     }
   }
 #undef SCVAE_D3
+#undef SCVAE_D3R
+#undef SCVAE_D3RK
 #undef SCVAE_D3C
 #undef SCVAE_D3KC
 #undef SCVAE_D3K

@@ -1813,6 +1813,75 @@ int gather_rows_f32(hipStream_t stream, const float* src, const int64_t* rows, i
   return 0;
 }
 
+// out[i, 0 .. cols) = src[rows[i], 0 .. cols) of a resident uint16 count matrix (64-bit row
+// offsets: the headline set is 2.25e9 elements).  Workgroup (i, part): row i, every gridDim.y-th
+// run of 256 16-byte pieces; VEC = false (a base or pitch off 16 bytes): element by element.  The
+// columns of `out` beyond cols are not written.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_rows_u16_kernel(
+    const uint16_t* __restrict__ src, int64_t ld_src, const int64_t* __restrict__ rows,
+    int64_t cols, uint16_t* __restrict__ out, int64_t ld_out) {
+  typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
+  const uint16_t* s = src + (size_t)rows[blockIdx.x] * (size_t)ld_src;
+  uint16_t* d = out + (size_t)blockIdx.x * (size_t)ld_out;
+  const int64_t first = (int64_t)blockIdx.y * 256 + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.y * 256;
+  if (VEC) {
+    const int64_t nvec = cols / 8;
+    for (int64_t v = first; v < nvec; v += stride)
+      reinterpret_cast<u32x4g*>(d)[v] = reinterpret_cast<const u32x4g*>(s)[v];
+    if (blockIdx.y == 0 && nvec * 8 + threadIdx.x < cols)   // (cols % 8 leftover elements)
+      d[nvec * 8 + threadIdx.x] = s[nvec * 8 + threadIdx.x];
+  } else {
+    for (int64_t c = first; c < cols; c += stride) d[c] = s[c];
+  }
+}
+// the same rows as fp32 (a count converts exactly): the minibatch of a step that takes no uint16
+// batch -- small minibatches, dropout on the input layer -- out of the resident matrix
+__global__ __launch_bounds__(256) void gather_rows_u16_f32_kernel(
+    const uint16_t* __restrict__ src, int64_t ld_src, const int64_t* __restrict__ rows,
+    int64_t cols, float* __restrict__ out, int64_t ld_out) {
+  const uint16_t* s = src + (size_t)rows[blockIdx.x] * (size_t)ld_src;
+  float* d = out + (size_t)blockIdx.x * (size_t)ld_out;
+  for (int64_t c = (int64_t)blockIdx.y * 256 + threadIdx.x; c < cols; c += (int64_t)gridDim.y * 256)
+    d[c] = (float)s[c];
+}
+int gather_rows_u16_f32(hipStream_t stream, const uint16_t* src, int64_t ld_src,
+                        const int64_t* rows, int64_t n, int64_t cols, float* out, int64_t ld_out) {
+  SCVAE_ARG(src && rows && out && n >= 0 && n <= INT32_MAX && cols >= 0 && ld_src >= cols &&
+            ld_out >= cols);
+  if (n == 0 || cols == 0) return 0;
+  const int64_t runs = (cols + 255) / 256;
+  int64_t parts = (2048 + n - 1) / n;
+  if (parts > runs) parts = runs;
+  hipLaunchKernelGGL(gather_rows_u16_f32_kernel, dim3((unsigned)n, (unsigned)parts), dim3(256), 0,
+                     stream, src, ld_src, rows, cols, out, ld_out);
+  SCVAE_LAUNCH_CHECK("gather_rows_u16_f32_kernel");
+  return 0;
+}
+int gather_rows_u16(hipStream_t stream, const uint16_t* src, int64_t ld_src, const int64_t* rows,
+                    int64_t n, int64_t cols, uint16_t* out, int64_t ld_out) {
+  SCVAE_ARG(src && rows && out && n >= 0 && n <= INT32_MAX && cols >= 0 && ld_src >= cols &&
+            ld_out >= cols);
+  if (n == 0 || cols == 0) return 0;
+  const bool vec = (((uintptr_t)src | (uintptr_t)out) & 15) == 0 && ((ld_src | ld_out) & 7) == 0;
+  // a row of 32 738 genes is 16 runs of 256 pieces: split rows over workgroups while the rows
+  // alone do not fill the device
+  const int64_t runs = vec ? (cols / 8 + 255) / 256 : (cols + 255) / 256;
+  int64_t parts = (1024 + n - 1) / n;
+  if (parts > runs) parts = runs;
+  if (parts < 1) parts = 1;
+  const dim3 grid((unsigned)n, (unsigned)parts);
+  if (vec)
+    hipLaunchKernelGGL(gather_rows_u16_kernel<true>, grid, dim3(256), 0, stream, src, ld_src, rows,
+                       cols, out, ld_out);
+  else
+    hipLaunchKernelGGL(gather_rows_u16_kernel<false>, grid, dim3(256), 0, stream, src, ld_src,
+                       rows, cols, out, ld_out);
+  SCVAE_LAUNCH_CHECK("gather_rows_u16_kernel");
+  return 0;
+}
+
 
 // ================================ dropout ==================================
 

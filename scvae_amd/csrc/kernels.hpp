@@ -27,9 +27,12 @@ int count_gemm(hipStream_t stream, int mode, const float* x, int ldx, int rows, 
                const float* other, int ld_other, int N, const float* bias, int act, float* C,
                int ldc, void* workspace, size_t workspace_bytes);
 // the same with x as uint16 counts (row pitch ldx even, base 4-byte aligned)
+// x_rows (optional, [rows]): x is a resident matrix of pitch ldx and row m of the product's x is
+// its row x_rows[m] (64-bit offsets; rows may repeat) -- bit-identical to the gathered rows
 int count_gemm_u16(hipStream_t stream, int mode, const uint16_t* x, int ldx, int rows, int cols,
                const float* other, int ld_other, int N, const float* bias, int act, float* C,
-               int ldc, void* workspace, size_t workspace_bytes);
+               int ldc, void* workspace, size_t workspace_bytes,
+               const int64_t* x_rows = nullptr);
 // The same minibatch as a list of its non-zeros grouped by (16 rows, 32 genes) -- count_gemm.hip
 // describes the format -- and the two products read from it (bit-identical to count_gemm_u16).
 struct CountTiles {
@@ -389,15 +392,19 @@ int decoder_fused2_launch(hipStream_t s, bool train, int kind, const float* d, i
                           int inline_lgamma, float* ll_part, float* dd_part);
 // arith: 0 fp32 MFMA, 1 the exact nine-term bf16 split where decoder_fused3 applies, 2 = 1 with
 // six-term products in the producer / consumer training kernel
+// the kernel decoder_fused_forward launches: 0 fp32 training kernels' forward half, 1
+// decoder_forward_kernel, 3 / 4 the forward forms of decoder_head3 / head4_kernel
+int decoder_forward_choice(int heads, int H, int arith);
 int decoder_fused_forward(hipStream_t s, int kind, const float* d, int rows, int H, HeadParams hp,
                           int F, Targets t, int B, const float* row_const, float* ll,
-                          float* workspace, int arith);
+                          float* workspace, int arith, const int64_t* t_rows = nullptr);
 int decoder_fused_train(hipStream_t s, int kind, const float* d, int rows, int H, HeadParams hp,
                         int F, Targets t, int B, const float* gw, const float* row_const,
                         float* ll, float* dd, float* workspace, int arith,
                         bool kernel_only = false,
                         const HeadDropout* drop = nullptr,    // drop: bf16x9 kernel only
-                        int dd_mode = 0);                     // 1: XCD-local atomics for dd
+                        int dd_mode = 0,                      // 1: XCD-local atomics for dd
+                        const int64_t* t_rows = nullptr);     // uint16 targets through a row index
 
 // training kernel on the bf16 matrix cores, exact nine-term split (decoder_fused3.hip)
 bool decoder_fused3_supported(int P, int H);
@@ -418,7 +425,10 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
                           HeadParams hp, int F, Targets t, int B, const float* gw,
                           int inline_lgamma, float* ll_part, float* dd_part, float* planes,
                           const HeadDropout* drop = nullptr, int cp_pass = 0,
-                          const CpRows* cp = nullptr, int dd_mode = 0, float* rg_slab = nullptr);
+                          const CpRows* cp = nullptr, int dd_mode = 0, float* rg_slab = nullptr,
+                          const int64_t* t_rows = nullptr);
+// t_rows (optional, with uint16 targets; [B]): t.p is a resident matrix and cell b of the
+// minibatch is its row t_rows[b] -- the ..._rows_kernel forms of the two bf16x9 kernels
 // rg_slab (decoder_fused3_rg_slab_floats(H, F) floats, or nullptr: one row group): where the
 // producer / consumer kernel's row groups behind the first leave their dW / db (decoder_fused3.hip,
 // "row groups")
@@ -458,7 +468,8 @@ int decoder_train_kernel(int P, int H, int arith);   // 1 / 2: the fp32 schedule
 // forward-only variant with the pre-activations in registers (decoder_forward.hip)
 bool decoder_forward_supported(int P, int H);
 int decoder_forward_launch(hipStream_t s, int kind, const float* d, int rows, int H, HeadParams hp,
-                           int F, Targets t, int B, int inline_lgamma, float* ll_part);
+                           int F, Targets t, int B, int inline_lgamma, float* ll_part,
+                           const int64_t* t_rows = nullptr);
 
 // ---- gmvae_kernels.hip ----
 int add_group_rows(hipStream_t s, const float* a0, const float* rows, float* out, int K, int B,
@@ -527,6 +538,11 @@ int csr_densify_u16(hipStream_t stream, const int64_t* indptr, const int32_t* in
 int csr_row_lgamma1p(hipStream_t stream, const int64_t* indptr, const float* values, int64_t n_rows,
                      float* out);
 int gather_rows_f32(hipStream_t stream, const float* src, const int64_t* rows, int B, float* out);
+// out[i, 0 .. cols) = src[rows[i], 0 .. cols): minibatch rows out of a resident uint16 matrix
+int gather_rows_u16(hipStream_t stream, const uint16_t* src, int64_t ld_src, const int64_t* rows,
+                    int64_t n, int64_t cols, uint16_t* out, int64_t ld_out);
+int gather_rows_u16_f32(hipStream_t stream, const uint16_t* src, int64_t ld_src,
+                        const int64_t* rows, int64_t n, int64_t cols, float* out, int64_t ld_out);
 
 // counter-based standard-normal draws (Philox4x32-10 + Box-Muller), keyed by
 // (seed, stream id, global row, column): identical for any sharding of the rows

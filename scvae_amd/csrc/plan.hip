@@ -295,7 +295,7 @@ int plan_gemm(scvae_plan* p, hipStream_t s, bool ta, bool tb, const float* A, co
         ? count_gemm_tiles(s, mode, p->step_tiles, p->step_u16, p->step_u16_ld, rows, cols, B, ldb,
                            N, bias, act, C, ldc, p->gemm_ws, p->gemm_ws_bytes)
         : count_gemm_u16(s, mode, p->step_u16, p->step_u16_ld, rows, cols, B, ldb, N,
-                         bias, act, C, ldc, p->gemm_ws, p->gemm_ws_bytes);
+                         bias, act, C, ldc, p->gemm_ws, p->gemm_ws_bytes, p->step_rows);
     stage_probe(mode ? PS_COUNT_DW : PS_COUNT_FWD, 1, s);
     return rc;
   }
@@ -1188,6 +1188,10 @@ static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
                      (!head_drop || (heads_fused_dropout_ok(p, n_iw) && !cpoisson)) &&
                      (c.likelihood <= LK_ZINB || c.likelihood == LK_BERNOULLI ||
                       (cpoisson && decoder_fused_cpoisson_supported(h1, p->head_arith)));
+  if (p->step_rows && (cpoisson || head_drop || (training && n_iw > 1))) {
+    set_error("a row index needs a plain single-pass step (scvae_plan_accepts_counts_rows)");
+    return -1;
+  }
   if (p->x_u16 && !fused) {
     set_error("the uint16 minibatch needs the fused likelihood kernels (no -k / constrained "
               "Poisson, evaluation statistics, or head dropout outside the bf16x9 kernel)");
@@ -1215,7 +1219,7 @@ static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
                                     a->row_const, p->ll, nullptr, p->fused_ws);
     if (fused)
       return decoder_fused_forward(s, c.likelihood, dch, R, h1, hp, F, tg, B, a->row_const, p->ll,
-                                   p->fused_ws, p->head_arith);
+                                   p->fused_ws, p->head_arith, p->step_rows);
     if (cat_forward)
       return decoder_fused_forward_cat(s, c.likelihood, KM, dch, R, h1, hp,
                                        p->params + p->head_k.w, p->params + p->head_k.b, F, a->t,
@@ -1293,7 +1297,7 @@ static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     else
       rc = decoder_fused_train(s, c.likelihood, dch, R, h1, hp, F, tg, B, p->gw, a->row_const,
                                p->ll, dcur, p->fused_ws, p->head_arith, false,
-                               head_drop ? &hdrop : nullptr, p->dd_atomics);
+                               head_drop ? &hdrop : nullptr, p->dd_atomics, p->step_rows);
     if (rc) return rc;
   } else if (fused_cat) {
     // (pre_k -- the logits' buffer of the unfused path -- is free: ll / dd of the second launch)
@@ -1924,6 +1928,35 @@ int scvae_plan_accepts_counts_u16(const scvae_plan* p, int64_t cells, int32_t tr
   return 1;
 }
 
+int32_t scvae_plan_accepts_counts_rows(const scvae_plan* p, int64_t cells, int32_t training) {
+  if (!scvae_plan_accepts_counts_u16(p, cells, training)) return 0;
+  const scvae_model_config& c = p->cfg;
+  // every reader of the minibatch has to take the index: the count kernels (any VAE step that
+  // passed the test above), and of the likelihood kernels the two bf16x9 ones with all nine terms
+  // and the fp32 forward kernel -- so: VAE, the four count likelihoods, one likelihood pass per
+  // step, no head dropout.  Everything else gathers (scvae_gather_rows_u16).
+  if (c.model_type != SCVAE_MODEL_VAE || c.likelihood > scvae::LK_ZINB || c.k_max > 0) return 0;
+  if (p->head_arith != 1 || training == 1) return 0;
+  const int H = p->heads[0].n_in;
+  if (training) {
+    if (p->heads[0].keep > 0.f) return 0;
+    return scvae::decoder_train_kernel(p->P, H, p->head_arith) == 3 ? 1 : 0;
+  }
+  // evaluation: the kernel decoder_fused_forward picks (its fp32 training-kernel form, choice 0,
+  // has no indexed variant)
+  return scvae::decoder_forward_choice(p->P, H, p->head_arith) != 0 ? 1 : 0;
+}
+
+int scvae_gather_rows_u16(const uint16_t* src, int64_t ld_src, const int64_t* rows, int64_t n,
+                          int64_t cols, uint16_t* out, int64_t ld_out, void* stream) {
+  return scvae::gather_rows_u16((hipStream_t)stream, src, ld_src, rows, n, cols, out, ld_out);
+}
+
+int scvae_gather_rows_u16_f32(const uint16_t* src, int64_t ld_src, const int64_t* rows, int64_t n,
+                              int64_t cols, float* out, int64_t ld_out, void* stream) {
+  return scvae::gather_rows_u16_f32((hipStream_t)stream, src, ld_src, rows, n, cols, out, ld_out);
+}
+
 int scvae_plan_step(scvae_plan* p, const scvae_step_args* a, void* stream) {
   SCVAE_ARG(p && a);
   SCVAE_ARG(p->params && p->ws);
@@ -1938,10 +1971,21 @@ int scvae_plan_step(scvae_plan* p, const scvae_step_args* a, void* stream) {
                        "(scvae_plan_accepts_counts_u16)");
       return -1;
     }
+    if (a->counts_rows &&
+        !scvae_plan_accepts_counts_rows(p, a->cells, a->training ? (single_pass ? 2 : 1) : 0)) {
+      scvae::set_error("this plan / step does not read its minibatch through a row index "
+                       "(scvae_plan_accepts_counts_rows): gather the rows (scvae_gather_rows_u16)");
+      return -1;
+    }
+    if (a->counts_rows && a->count_tiles) {
+      scvae::set_error("count tiles do not go with a row index");
+      return -1;
+    }
     // (whole 64-gene strips: the likelihood kernels read four counts per lane without a bound)
     SCVAE_ARG(a->counts_ld >= (p->cfg.feature_size + 63) / 64 * 64 && (a->counts_ld & 7) == 0 &&
               ((uintptr_t)a->counts_u16 & 15) == 0);
   }
+  SCVAE_ARG(u16 || !a->counts_rows);
   SCVAE_ARG(a->n_iw > 0 && a->n_mc > 0);
   SCVAE_ARG(a->deterministic_z || (int64_t)a->n_iw * a->n_mc <= p->max_samples);
   SCVAE_ARG(a->deterministic_z || a->eps);
@@ -1953,6 +1997,7 @@ int scvae_plan_step(scvae_plan* p, const scvae_step_args* a, void* stream) {
   p->x_u16 = u16;
   p->step_u16 = a->counts_u16;
   p->step_u16_ld = (int)a->counts_ld;
+  p->step_rows = u16 ? a->counts_rows : nullptr;
   p->step_tiles = scvae::CountTiles();
   if (a->count_tiles) {
     SCVAE_ARG(u16 && a->count_tiles->entries && a->count_tiles->tile_ptr &&
@@ -2010,8 +2055,9 @@ int scvae_plan_step(scvae_plan* p, const scvae_step_args* a, void* stream) {
       const size_t x_bytes = (size_t)a->cells * Fsz * sizeof(float);
       SCVAE_ARG(!overlaps(w->fetch_out, out_bytes, a->x, x_bytes) &&
                 !overlaps(w->fetch_out, out_bytes, a->t, x_bytes) &&
-                !overlaps(w->fetch_out, out_bytes, a->counts_u16,
-                          (size_t)a->cells * (size_t)a->counts_ld * 2) &&
+                (a->counts_rows != nullptr ||     // (a resident matrix: its extent is not known here)
+                 !overlaps(w->fetch_out, out_bytes, a->counts_u16,
+                           (size_t)a->cells * (size_t)a->counts_ld * 2)) &&
                 !overlaps(w->fetch_row_values_out, (size_t)w->fetch_n * sizeof(float),
                           a->row_const, (size_t)a->cells * sizeof(float)));
     }

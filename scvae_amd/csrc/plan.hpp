@@ -169,6 +169,8 @@ struct scvae_plan {
   bool x_u16 = false;            // this step's minibatch is the uint16 count matrix below
   scvae::CountTiles step_tiles;  // ... and, when ent != nullptr, the same rows as tile-indexed non-zeros
   const uint16_t* step_u16 = nullptr;
+  // ... read through a row index: step_u16 is a resident matrix, cell m its row step_rows[m]
+  const int64_t* step_rows = nullptr;
   int step_u16_ld = 0;
   // scvae_step_args.side: the plan's second stream, forked where the likelihood heads' gradients
   // are final and joined before the step ends

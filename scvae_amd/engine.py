@@ -464,6 +464,18 @@ class Engine:
         return bool(self.lib.scvae_plan_accepts_counts_u16(
             self.handle, int(cells), mode))
 
+    def accepts_counts_rows(self, cells, training, n_iw=None):
+        """Whether a step of ``cells`` cells may read its minibatch out of a
+        resident uint16 matrix through a row index (``step(counts_rows=)``):
+        every kernel that streams the minibatch takes the index, no dense copy
+        of the minibatch is made.  Never true where ``accepts_counts_u16`` is
+        false; where it is false the caller gathers the rows
+        (``DeviceCSR.gather_counts_u16`` from the resident matrix)."""
+        self.reserve(int(cells), 1)
+        mode = 0 if not training else (2 if n_iw == 1 else 1)
+        return bool(self.lib.scvae_plan_accepts_counts_rows(
+            self.handle, int(cells), mode))
+
     def set_sync(self, callback):
         """Install the data-parallel collective hook (see scvae_sync_fn)."""
         if callback is None:
@@ -480,7 +492,7 @@ class Engine:
              decoder_extra=None, dropout_seed=None, count_sum=None,
              row_offset=0, x_counts=False, learning_rate=None,
              grad_scale=1.0, next_minibatch=None, next_noise=None,
-             count_tiles=None):
+             count_tiles=None, counts_rows=None):
         """One graph execution (no host synchronisation).  ``outputs`` maps
         optional output names of ``scvae_step_args`` to preallocated tensors.
         ``dropout_seed``: seed of this training step's dropout masks (default:
@@ -496,8 +508,22 @@ class Engine:
         ``next_noise`` -- ``dict(out=, block_stride=, row_offset=, seed=,
         stream_id=)`` for its noise (``philox_normal_blocks`` arguments).
         ``count_tiles``: this step's uint16 minibatch also as a
-        ``minibatch.CountTiles`` (same rows)."""
+        ``minibatch.CountTiles`` (same rows).
+        ``counts_rows`` (int64 ``[cells]``, device): ``x`` (uint16, also ``t``)
+        is a RESIDENT matrix and row ``m`` of this step's minibatch is its row
+        ``counts_rows[m]``; ``row_const`` stays in minibatch order.  Only where
+        ``accepts_counts_rows`` says so."""
         cells = x.shape[0]
+        if counts_rows is not None:
+            if (x.dtype != torch.uint16 or counts_rows.dtype != torch.int64
+                    or counts_rows.dim() != 1
+                    or not counts_rows.is_contiguous()
+                    or counts_rows.device != x.device):
+                raise ValueError("counts_rows: a contiguous int64 [cells] "
+                                 "index into a uint16 matrix on its device")
+            if count_tiles is not None:
+                raise ValueError("count tiles do not go with a row index")
+            cells = int(counts_rows.numel())
         samples = 1 if deterministic_z else n_iw * n_mc
         self.reserve(cells, samples)
         a = _lib.StepArgs()
@@ -508,6 +534,8 @@ class Engine:
                 raise ValueError("a uint16 minibatch is both x and t")
             a.counts_u16 = x.data_ptr()
             a.counts_ld = x.stride(0)
+            if counts_rows is not None:
+                a.counts_rows = counts_rows.data_ptr()
             # the same rows as tile-indexed non-zeros (minibatch.CountTiles):
             # the input layer's two products read them instead of the batch
             if count_tiles is not None:

@@ -149,11 +149,20 @@ class DeviceCSR:
         return int(self.values.numel())
 
     def gather_dense(self, rows, out=None, row_const_out=None):
-        """Dense fp32 ``[len(rows), F]`` minibatch (and its lgamma row term)."""
+        """Dense fp32 ``[len(rows), F]`` minibatch (and its lgamma row term);
+        converted out of the resident uint16 matrix when there is one."""
         n, F = int(rows.numel()), self.shape[1]
         if out is None:
             out = torch.empty((n, F), dtype=torch.float32, device=self.device)
         stream = current_stream_handle(self.device)
+        dense = self.resident_u16
+        if dense is not None:
+            _lib.check(self.lib.scvae_gather_rows_u16_f32(
+                _ptr(dense), dense.stride(0), _ptr(rows), n, F, _ptr(out),
+                out.stride(0), stream), "scvae_gather_rows_u16_f32")
+            if row_const_out is not None:
+                self.gather_row_constants(rows, row_const_out)
+            return out
         _lib.check(self.lib.scvae_csr_minibatch(
             _ptr(self.indptr), _ptr(self.indices), _ptr(self.values),
             _ptr(rows), n, F, _ptr(out), out.stride(0), 0,
@@ -174,16 +183,91 @@ class DeviceCSR:
         """Row pitch (elements) of the uint16 minibatch: whole 128-byte lines."""
         return (self.shape[1] + 63) // 64 * 64
 
+    #: (dense uint16 [rows, u16_pitch], row constants [rows], host flags of the
+    #: rows written so far) once ``resident_counts_u16`` or an evaluation pass
+    #: (models/base.py, ``_evaluation_resident``) has made it: ONE copy serves
+    #: the training steps and the epoch-end evaluation of the same set
+    _evaluation_resident = None
+    #: ``gather_counts_u16`` copies from that matrix only once
+    #: ``resident_counts_u16`` has been asked for it (the opt-in)
+    _gather_from_resident = False
+
+    def resident_counts_u16(self, chunk=4096):
+        """The whole matrix as uint16 counts ``[rows, u16_pitch]`` (pad
+        columns zero) held on the device, built in chunks of rows with the
+        densify kernel -- what ``Engine.step(counts_rows=)`` indexes and
+        ``gather_counts_u16`` then copies from.  Returns the tensor.  Shared
+        with the evaluation passes' resident copy: rows they have written are
+        not written again."""
+        if not self.integer_counts:
+            raise ValueError("not an integer count matrix below 65 536")
+        n = self.shape[0]
+        held = self._evaluation_resident
+        if held is None or held[0].shape[0] != n:
+            held = (torch.empty(n, self.u16_pitch, dtype=torch.uint16,
+                                device=self.device),
+                    torch.empty(n, device=self.device),
+                    numpy.zeros(n, dtype=bool))
+        dense, constants, filled = held
+        # (the fetches below walk the CSR rows; a copy the evaluation passes
+        #  hold stays published while its missing rows are written)
+        self._gather_from_resident = False
+        for first in range(0, n, int(chunk)):
+            last = min(first + int(chunk), n)
+            if filled[first:last].all():
+                continue
+            rows = torch.arange(first, last, device=self.device,
+                                dtype=torch.int64)
+            self.gather_counts_u16(rows, out=dense[first:last],
+                                   row_const_out=constants[first:last])
+            filled[first:last] = True
+        self._evaluation_resident = held
+        # from here on gather_counts_u16 / gather_dense of THIS object copy
+        # from the matrix (model.train uploads its DeviceCSR per call, so the
+        # switch lives as long as the run that asked for it)
+        self._gather_from_resident = True
+        return dense
+
+    def gather_row_constants(self, rows, out):
+        """``out[i]`` <- the lgamma row term of row ``rows[i]`` (the
+        ``row_const`` of a step that reads its minibatch through ``rows``)."""
+        _lib.check(self.lib.scvae_gather_rows(
+            _ptr(self.row_lgamma1p), _ptr(rows), int(rows.numel()), _ptr(out),
+            current_stream_handle(self.device)), "scvae_gather_rows")
+        return out
+
+    @property
+    def resident_u16(self):
+        """The resident uint16 matrix ``resident_counts_u16`` built (every
+        row written), else None."""
+        held = self._evaluation_resident
+        if (not self._gather_from_resident or held is None
+                or not held[2].all()):
+            return None
+        return held[0]
+
     def gather_counts_u16(self, rows, out=None, row_const_out=None):
         """The minibatch as uint16 counts ``[len(rows), u16_pitch]`` (columns past
         F zeroed) for the kernels that stream it -- integer count matrices only
-        (``integer_counts``).  Pass it to ``Engine.step`` as both x and t."""
+        (``integer_counts``).  Pass it to ``Engine.step`` as both x and t.
+        Copied out of the resident matrix (``resident_counts_u16``) when there
+        is one -- the same values, no walk of the CSR rows."""
         if not self.integer_counts:
             raise ValueError("not an integer count matrix below 65 536")
         n, F, ld = int(rows.numel()), self.shape[1], self.u16_pitch
         if out is None:
             out = torch.empty((n, ld), dtype=torch.uint16, device=self.device)
         stream = current_stream_handle(self.device)
+        dense = self.resident_u16
+        if dense is not None and out.stride(0) >= ld:
+            _lib.check(self.lib.scvae_gather_rows_u16(
+                _ptr(dense), dense.stride(0), _ptr(rows), n, ld, _ptr(out),
+                out.stride(0), stream), "scvae_gather_rows_u16")
+            if row_const_out is not None:
+                _lib.check(self.lib.scvae_gather_rows(
+                    _ptr(self.row_lgamma1p), _ptr(rows), n,
+                    _ptr(row_const_out), stream), "scvae_gather_rows")
+            return out
         _lib.check(self.lib.scvae_csr_minibatch(
             _ptr(self.indptr), _ptr(self.indices), _ptr(self.values),
             _ptr(rows), n, F, _ptr(out), out.stride(0), 1,

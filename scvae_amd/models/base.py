@@ -262,8 +262,14 @@ class ModelBase:
     # ======================================================================
     def train(self, training_set, validation_set=None, number_of_epochs=None,
               minibatch_size=None, learning_rate=None, run_id=None,
-              new_run=None, reset_training=None, **kwargs):
-        """Train model (signature and behaviour of va:640-1599)."""
+              new_run=None, reset_training=None,
+              resident_training_set=False, **kwargs):
+        """Train model (signature and behaviour of va:640-1599).
+        ``resident_training_set`` (not in the reference): keep the training
+        set's dense uint16 rows on the device -- one copy, shared with the
+        epoch-end evaluation pass -- and let every step read its minibatch out
+        of it through a row index (or, where the plan has no indexed kernels,
+        a row gather) instead of densifying CSR rows; same results."""
         dm = defaults["models"]
         if number_of_epochs is None:
             number_of_epochs = dm["number_of_epochs"]
@@ -526,6 +532,25 @@ class ModelBase:
                 max(local_batch, 1), x_train.u16_pitch, dtype=torch.uint16,
                 device=device) for _ in range(2)]
 
+        # opt-in: the whole training set as resident uint16 rows; a step then
+        # takes "that matrix + its row index" (the direct path) where every
+        # kernel that streams the minibatch reads through the index, else its
+        # rows copied out of the matrix (the gather) -- no CSR walk either way
+        self._training_resident_hits = 0
+        self._training_resident_gathers = 0
+        self._training_resident_address = None
+        resident_matrix = None
+        if resident_training_set:
+            why = self._training_resident_refusal(
+                x_train, t_train, noisy_preprocess)
+            if why is None:
+                resident_matrix = x_train.resident_counts_u16()
+                # (address only: what the epoch-end pass reads is compared
+                #  against it, _evaluation_resident_address)
+                self._training_resident_address = resident_matrix.data_ptr()
+            else:
+                say("Resident training set not used: {}.".format(why))
+
         def minibatch_buffers(slot, cells):
             """(x, t, row constant, fetch request or None) of a minibatch of
             ``cells`` cells in buffer set ``slot``."""
@@ -599,7 +624,30 @@ class ModelBase:
                 cells = int(rows.numel())
                 xb, tb, rc = minibatch_buffers(slot, cells)
                 eps = noise_buffer(slot, cells)
-                if not carried:   # (the previous step brought this minibatch)
+                counts_rows = None
+                if resident_matrix is not None:
+                    # (row constants in minibatch order either way; the noise
+                    #  still rides with the previous step)
+                    if (xb.dtype == torch.uint16
+                            and engine.accepts_counts_rows(cells, True,
+                                                           n_iw=n_iw)):
+                        x_train.gather_row_constants(rows, rc)
+                        xb = tb = resident_matrix
+                        counts_rows = rows.contiguous()
+                        self._training_resident_hits += 1
+                    elif xb.dtype == torch.uint16:
+                        x_train.gather_counts_u16(rows, out=xb,
+                                                  row_const_out=rc)
+                        self._training_resident_gathers += 1
+                    else:
+                        # (a step that takes no uint16 minibatch: the same
+                        #  rows converted to fp32)
+                        x_train.gather_dense(rows, out=tb, row_const_out=rc)
+                        self._training_resident_gathers += 1
+                    if not carried:
+                        self._draw_noise(eps, samples, cells, global_cells,
+                                         lo, step)
+                elif not carried:   # (the previous step brought this minibatch)
                     if xb is tb:
                         t_train.request(rows, tb, rc).issue()
                     else:
@@ -613,7 +661,8 @@ class ModelBase:
                     n_rows, n_global, n_lo = batches[index + 1]
                     n_cells = int(n_rows.numel())
                     n_xb, _, n_rc = minibatch_buffers(slot ^ 1, n_cells)
-                    next_minibatch = t_train.request(n_rows, n_xb, n_rc)
+                    if resident_matrix is None:
+                        next_minibatch = t_train.request(n_rows, n_xb, n_rc)
                     next_noise = self._noise_request(
                         noise_buffer(slot ^ 1, n_cells), samples, n_cells,
                         n_global, n_lo, step + 1)
@@ -634,7 +683,8 @@ class ModelBase:
                     # single process: clip + Adam ride with the step; data
                     # parallel: the gradient all-reduce comes first
                     learning_rate=learning_rate if sync is None else None,
-                    next_minibatch=next_minibatch, next_noise=next_noise)
+                    next_minibatch=next_minibatch, next_noise=next_noise,
+                    counts_rows=counts_rows)
                 if sync is not None:
                     sync.all_reduce_gradients()
                     engine.adam_step(learning_rate)
@@ -919,6 +969,8 @@ class ModelBase:
         resident = (self._evaluation_resident(x, n)
                     if u16_buffer is not None
                     and data_set.noisy_preprocess is None else None)
+        self._evaluation_resident_address = (
+            resident[0].data_ptr() if resident is not None else None)
         self._evaluation_counter = getattr(
             self, "_evaluation_counter", 0) + 1
         noise_stream = (1 << 40) + self._evaluation_counter * (1 << 20)
@@ -1055,6 +1107,32 @@ class ModelBase:
     # the 288; never more than a quarter of what is free when the set is first met
     evaluation_resident_bytes = 64 << 30
     _evaluation_resident_hits = 0     # steps that found their minibatch there
+    # the same budget rule for train(resident_training_set=True)
+    training_resident_bytes = evaluation_resident_bytes
+    _training_resident_hits = 0       # steps that read the matrix through an index
+    _training_resident_gathers = 0    # steps whose rows were copied out of it
+    _training_resident_address = None     # data_ptr of that matrix, and of the one the
+    _evaluation_resident_address = None   # last evaluation pass read its views from
+
+    def _training_resident_refusal(self, x, t, noisy_preprocess):
+        """None if ``train(resident_training_set=True)`` can keep the training
+        set resident, else the reason (one line) why it trains as without."""
+        if x is not t or noisy_preprocess:
+            return ("the input and the target of a step have to be the same "
+                    "matrix, without noisy preprocessing")
+        if not (getattr(x, "integer_counts", False)
+                and hasattr(x, "resident_counts_u16")):
+            return "not an integer count matrix below 65 536"
+        held = getattr(x, "_evaluation_resident", None)
+        n = x.shape[0]
+        if held is not None and held[0].shape[0] == n:
+            return None      # (the evaluation passes hold it already)
+        need = n * x.u16_pitch * 2 + n * 4
+        free, _ = torch.cuda.mem_get_info(self.engine.device)
+        if need > min(int(self.training_resident_bytes), free // 4):
+            return ("{:.1f} GB beyond the budget (training_resident_bytes, a "
+                    "quarter of the free device memory)".format(need / 1e9))
+        return None
 
     def _evaluation_resident(self, x, n):
         """(dense uint16 [n, pitch], row constants [n], filled [n] host flags)
