@@ -412,8 +412,14 @@ int32_t scvae_plan_accepts_counts_rows(const scvae_plan* plan, int64_t cells, in
 int scvae_plan_decode(scvae_plan* plan, const float* z, int64_t rows, float* p_x_mean,
                       void* stream);
 
-/* _setup_optimiser (va:2736-2770): g <- clip(g*grad_scale, +-1); tf.train.AdamOptimizer
- * with lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the caller. */
+/* _setup_optimiser (va:2736-2770): with gc = clip(g*grad_scale, +-1), tf.train.AdamOptimizer's
+ *   m <- beta1*m + (1-beta1)*gc,  v <- beta2*v + (1-beta2)*gc*gc,
+ *   theta <- theta - lr_t*m/(sqrt(v) + epsilon),
+ * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the caller (t = 1 for the first update).
+ * theta, m and v [n] are updated in place.  grad is only READ: the clipped value is never
+ * stored, the buffer holds the caller's gradient after the call as before (a data-parallel
+ * caller reads it afterwards).  All four pointers 16-byte aligned (-1 otherwise, nothing is
+ * launched); any n >= 0. */
 int scvae_adam_clip_step(float* theta, float* grad, float* m, float* v, int64_t n,
                          float grad_scale, float lr_t, float beta1, float beta2, float epsilon,
                          void* stream);

@@ -14,6 +14,7 @@ import torch
 
 from oracle import likelihoods as lk
 from oracle import models as om
+from _parity import close_elementwise, close_maxnorm, close_scalar
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +84,89 @@ def test_batch_norm_stats_apply_and_backward(cuda_device, rows, N, relu):
     assert live.double().mean() > 0.99
     _close(da * live.to(cuda_device), at.grad * live, 5e-4 if relu else 2e-5, "da")
     _close(dbeta, bt.grad, 5e-4 if relu else 2e-5, "dbeta")
+
+
+# The longest chain of fp32 roundings a value passes through in the chunked
+# sums of scvae_bn_stats for up to 5000 rows (elementwise.hip: at most 5 + 16
+# additions within a chunk, a division, 4 + 16 across the chunks, a division: 43)
+BN_SUM_ROUNDINGS = 48
+U32 = 2.0 ** -24
+
+
+@pytest.mark.parametrize("rows", [37, 4096, 5000])
+def test_batch_norm_stats_under_cancellation(cuda_device, rows):
+    """Columns whose mean dwarfs their spread, constant columns and a single
+    spike, against the fp64 statistics of the fp32-ROUNDED inputs (fp32 holds
+    1e4 to 1e-3: the unrounded oracle would be a different column).
+
+    With u = 2^-24, k = BN_SUM_ROUNDINGS and A = mean |x| of a column:
+      mean: a sum of terms of magnitude A through at most k roundings:
+            |d mean| <= k u A =: D  (a few ulps of the mean where A = |mean|)
+      var:  the kernel centres every chunk on its own mean and merges with
+            M2 + n (mean_c - mean)^2.  A chunk mean off by d_c leaves
+            sum (x - mean_c - d_c)^2 = M2_c + n d_c^2 (the cross term vanishes)
+            and moves the merge term by 2 n d_c (mean_c - mean) + n d_c^2; the
+            global mean's own error D adds as much again.  Over the chunks,
+            with mean_c |mean_c - mean| <= sigma:
+            |d var| <= 2 D sigma + 4 D^2 + k u var
+            (the last term: the roundings of the sums of squares, all positive).
+    Nothing in it grows with mean^2.  A one-pass E[x^2] - E[x]^2 loses
+    mean^2 u ~ 6 on the first column and 0.5 on the second, against bounds of
+    about 0.05 and 1e-3."""
+    from scvae_amd import _lib
+    lib = _lib.load()
+    N = 7
+    rng = np.random.default_rng(rows)
+    a = np.zeros((rows, N))
+    a[:, 0] = rng.normal(1e4, 1.0, rows)
+    a[:, 1] = rng.normal(-3e3, 0.05, rows)
+    a[:, 2] = 2.5        # (every partial sum and the quotient exact: var == 0)
+    a[:, 3] = 0.0
+    a[:, 4] = rng.normal(0.0, 1.0, rows)
+    a[rows // 3, 5] = 1000.0
+    a[:, 6] = rng.normal(0.3, 2.0, rows)
+    a32 = a.astype(np.float32)
+    beta = rng.normal(0, 0.5, N).astype(np.float32)
+    ad = torch.from_numpy(a32).to(cuda_device)
+    bd = torch.from_numpy(beta).to(cuda_device)
+    ws = torch.empty(int(lib.scvae_bn_workspace_floats(N)), device=cuda_device)
+    mean = torch.empty(N, device=cuda_device)
+    var = torch.empty(N, device=cuda_device)
+    h = torch.empty(rows, N, device=cuda_device)
+    _lib.check(lib.scvae_bn_stats(_p(ad), N, rows, N, _p(mean), _p(var), _p(ws), _stream()),
+               "bn_stats")
+    _lib.check(lib.scvae_bn_apply_relu_fwd(_p(ad), N, _p(mean), _p(var), _p(bd), _p(h), N,
+                                           rows, N, 0, _stream()), "bn_apply_fwd")
+    torch.cuda.synchronize()
+    x = a32.astype(np.float64)
+    want_mean, want_var = x.mean(axis=0), x.var(axis=0)
+    D = BN_SUM_ROUNDINGS * U32 * np.abs(x).mean(axis=0)
+    var_tol = 2 * D * np.sqrt(want_var) + 4 * D * D + BN_SUM_ROUNDINGS * U32 * want_var
+    got_mean, got_var = mean.cpu().double().numpy(), var.cpu().double().numpy()
+    print("bn_stats rows={}: mean err / bound {}, var err / bound {}".format(
+        rows, np.abs(got_mean - want_mean) / np.maximum(D, 1e-300),
+        np.abs(got_var - want_var) / np.maximum(var_tol, 1e-300)))
+    for c in range(N):
+        close_scalar(got_mean[c], want_mean[c], rtol=0.0, atol=D[c],
+                     what="mean of column {}".format(c))
+        close_scalar(got_var[c], want_var[c], rtol=0.0, atol=var_tol[c],
+                     what="variance of column {}".format(c))
+    assert (got_var >= 0).all()
+    # the constant columns: mean exact, variance exactly 0, the output beta
+    assert got_mean[2] == 2.5 and got_mean[3] == 0.0
+    assert got_var[2] == 0.0 and got_var[3] == 0.0
+    hh = h.cpu().numpy()
+    assert (hh[:, 2] == beta[2]).all() and (hh[:, 3] == beta[3]).all()
+    # the normalisation on the statistics THE DEVICE holds: a - mean (1
+    # rounding), var + 1e-3 (1, halved by the root), the reciprocal root (the
+    # hardware's v_rsq_f32: 1 ulp = 2 u), the multiply-add (1): 5 u of
+    # |a - mean| / sqrt(var + 1e-3) + |beta|, allowed twice
+    istd = 1.0 / np.sqrt(got_var + np.float64(np.float32(om.BN_EPSILON)))
+    want_h = (x - got_mean) * istd + beta.astype(np.float64)
+    mag = np.abs(x - got_mean) * istd + np.abs(beta.astype(np.float64))
+    close_elementwise((hh.astype(np.float64) - want_h) / np.maximum(mag, 1e-300),
+                      np.zeros_like(want_h), rtol=0.0, atol=2 * 5 * U32,
+                      what="h relative to its terms")
 
 
 @pytest.mark.parametrize("K,S,B,L", [(3, 1, 48, 5), (20, 2, 64, 100), (2, 3, 7, 130)])
@@ -173,6 +257,45 @@ def test_categorical_entropy_kl(cuda_device, B, K, prior):
     _close(dl0, lt2.grad, 5e-5, "dlogits (gate off)")
 
 
+def _iw_inputs(n_iw, n_mc, B, per_sample, spread=None):
+    rng = np.random.default_rng(n_iw * 10 + n_mc + B)
+    ll = rng.normal(-300, 30, (n_iw, n_mc, B))
+    if spread is not None:      # importance samples nats apart
+        ll = ll + np.asarray(spread, dtype=np.float64).reshape(n_iw, 1, 1)
+    kl = rng.gamma(2.0, 2.0, (n_iw, n_mc, B) if per_sample else (B,))
+    # (as the fp32 values the device holds)
+    return (ll.astype(np.float32).astype(np.float64),
+            kl.astype(np.float32).astype(np.float64))
+
+
+def _iw_oracle(ll, kl, per_sample, w):
+    """va:2717-2734 with mu:129-137 (log_reduce_exp_mean over the importance
+    samples): the four means and d(-lower_bound_weighted) / d ll."""
+    B = ll.shape[-1]
+    lt = torch.from_numpy(ll).requires_grad_(True)
+    kt = torch.from_numpy(kl)
+    kk = kt if per_sample else kt.reshape(1, 1, B)
+    lb = om.log_reduce_exp_mean(lt - kk, 0).mean()
+    lbw = om.log_reduce_exp_mean(lt - w * kk, 0).mean()
+    (-lbw).backward()
+    return lb.item(), lbw.item(), ll.mean(), kl.mean(), lt.grad
+
+
+def _iw_run(device, ll, kl, per_sample, w, row_scale, with_gw, scalars=None):
+    from scvae_amd import _lib
+    lib = _lib.load()
+    n_iw, n_mc, B = ll.shape
+    lld, kld = _dev(ll, device), _dev(kl, device)
+    if scalars is None:
+        scalars = torch.zeros(8, device=device)
+    gw = torch.full((n_iw * n_mc * B,), float("nan"), device=device) if with_gw else None
+    _lib.check(lib.scvae_iw_logmeanexp(_p(lld), _p(kld), per_sample, n_iw, n_mc, B, w,
+                                       row_scale, _p(scalars), _p(gw), _stream()),
+               "iw_logmeanexp")
+    torch.cuda.synchronize()
+    return scalars, gw
+
+
 @pytest.mark.parametrize("n_iw,n_mc,B,per_sample", [
     (1, 1, 100, 0), (5, 1, 64, 0), (3, 2, 50, 1), (4, 3, 1000, 0), (2, 1, 4096, 1)])
 def test_iw_logmeanexp(cuda_device, n_iw, n_mc, B, per_sample):
@@ -203,6 +326,97 @@ def test_iw_logmeanexp(cuda_device, n_iw, n_mc, B, per_sample):
     assert abs(s[2] - ll.mean()) <= 2e-6 * abs(ll.mean())
     assert abs(s[3] - kl.mean()) <= 1e-5 * abs(kl.mean())
     _close(gw.reshape(n_iw, n_mc, B), lt.grad, 2e-5, "gw")
+
+
+def _iw_hold_scalars(scalars, want, share, what):
+    """The bounds of ``test_iw_logmeanexp``: 2e-6 relative, 1e-5 for the KL
+    mean; a rank holding 1 / ``share`` of the global minibatch emits that share
+    of the means."""
+    s = scalars.cpu().double().numpy()
+    assert np.isfinite(s[:4]).all(), what
+    for i, (name, rtol) in enumerate((("lower_bound", 2e-6), ("lower_bound_weighted", 2e-6),
+                                      ("reconstruction_error", 2e-6),
+                                      ("kl_divergence", 1e-5))):
+        close_scalar(s[i], want[i] / share, rtol=rtol, what="{} {}".format(what, name))
+    assert s[7] == 0.0, what
+
+
+# (n_iw, n_mc, B, per_sample, with a gw buffer).  Without one and with n_iw = 1
+# and the analytic KL the kernel takes the training step's path: eight loads in
+# flight per thread, 8192 pairs per trip -- (1, 3, 4096) and (1, 2, 4500) make a
+# second trip with a partly clamped tail, and B < pairs keeps the KL sum to the
+# first B pairs.  The others run the general loop: B = 1, 1024 mod B != 0, more
+# pairs than threads, with and without the gradient.
+IW_CASES = [
+    (1, 1, 1, 0, False), (1, 1, 100, 0, False), (1, 3, 4096, 0, False),
+    (1, 2, 4500, 0, False), (3, 2, 1500, 0, False), (3, 2, 1500, 1, False),
+    (3, 2, 1500, 0, True), (3, 2, 1500, 1, True), (2, 1, 1, 0, True),
+    (2, 1, 1, 1, True), (4, 1, 700, 0, True)]
+
+
+@pytest.mark.parametrize("share", [1, 3], ids=["whole", "third"])
+@pytest.mark.parametrize("w", [0.0, 0.6, 1.0])
+@pytest.mark.parametrize("n_iw,n_mc,B,per_sample,with_gw", IW_CASES)
+def test_iw_logmeanexp_paths(cuda_device, n_iw, n_mc, B, per_sample, with_gw, w, share):
+    ll, kl = _iw_inputs(n_iw, n_mc, B, per_sample)
+    row_scale = 1.0 / (n_mc * share * B)
+    scalars, gw = _iw_run(cuda_device, ll, kl, per_sample, w, row_scale, with_gw)
+    want = _iw_oracle(ll, kl, per_sample, w)
+    _iw_hold_scalars(scalars, want, share, "iw {} mc {} B {}".format(n_iw, n_mc, B))
+    if with_gw:     # (test_iw_logmeanexp's bound)
+        close_maxnorm(gw.reshape(n_iw, n_mc, B), want[4] / share, rtol=2e-5, what="gw")
+
+
+@pytest.mark.parametrize("w", [0.0, 0.6, 1.0])
+def test_iw_logmeanexp_samples_far_apart(cuda_device, w):
+    """Importance samples 50 to 1000 nats apart: the winner takes the weight.
+    Every weight is compared on its own.  With a = ll - w kl (of size up to
+    1300, where an fp32 ulp is 1.2e-4) and weight_r = exp(a_r - max a) / sum:
+    a_r carries two roundings of |w kl| + |a_r|, and so does the winner's,
+    which the sum inherits; the argument a_r - max a rounds once and the fast
+    exponential scales its argument by log2(e) in fp32 (2 more of |arg|); the
+    exponential itself, the sum, the division and the scale about 6 more:
+      |d weight_r| / weight_r <= u (2 (|a_r| + |w kl|) + 2 (|a_max| + |w kl|)
+                                    + 3 |a_r - a_max| + 6),  allowed twice,
+    plus one fp32 ulp of the winner's weight (row_scale, at most) as the
+    absolute term: 0 is a correct fp32 answer for e^-400."""
+    n_iw, n_mc, B = 5, 1, 64
+    ll, kl = _iw_inputs(n_iw, n_mc, B, 0, spread=[0, -50, -200, -400, -1000])
+    row_scale = 1.0 / (n_mc * B)
+    scalars, gw = _iw_run(cuda_device, ll, kl, 0, w, row_scale, True)
+    want = _iw_oracle(ll, kl, 0, w)
+    _iw_hold_scalars(scalars, want, 1, "far apart")
+    g = want[4].numpy()
+    assert (np.abs(g).argmax(axis=0) == 0).mean() > 0.5      # (sample 0 mostly wins)
+    wkl = np.abs(w * kl).reshape(1, 1, B)
+    a = ll - w * kl.reshape(1, 1, B)
+    top = a.max(axis=0, keepdims=True)
+    rel = 2 * U32 * (2 * (np.abs(a) + wkl) + 2 * (np.abs(top) + wkl)
+                     + 3 * np.abs(a - top) + 6)
+    got = gw.reshape(n_iw, n_mc, B).cpu().double().numpy()
+    assert np.isfinite(got).all()
+    excess = np.abs(got - g) - (rel * np.abs(g) + row_scale * 2.0 ** -23)
+    assert excess.max() <= 0, (np.unravel_index(excess.argmax(), excess.shape),
+                               excess.max())
+
+
+@pytest.mark.parametrize("with_gw", [False, True], ids=["step-path", "general-path"])
+def test_iw_logmeanexp_counts_non_finite_bounds(cuda_device, with_gw):
+    """scalars[7] counts the calls since the caller zeroed it whose bound was
+    not finite (plain float arithmetic on a -inf log-likelihood)."""
+    ll, kl = _iw_inputs(1, 2, 300, 0)
+    bad = ll.copy()
+    bad[0, 1, 17] = -np.inf
+    scalars = torch.zeros(8, device=cuda_device)
+    want = _iw_oracle(ll, kl, 0, 0.6)
+    for values, count in ((ll, 0.0), (bad, 1.0), (bad, 2.0), (ll, 2.0)):
+        _iw_run(cuda_device, values, kl, 0, 0.6, 1.0 / 600, with_gw, scalars)
+        s = scalars.cpu().double().numpy()
+        assert s[7] == count, (s[7], count)
+        if values is ll:
+            close_scalar(s[0], want[0], rtol=2e-6, what="lower_bound")
+        else:
+            assert not np.isfinite(s[0])
 
 
 @pytest.mark.parametrize("likelihood", ["poisson", "negative binomial",
