@@ -79,7 +79,12 @@ typedef struct scvae_model_config {
                                  is the constant 0 and POSTERIOR/LOG_SIGMA is not built.
                                  GMVAE: bit 2 (value 4) "legacy gaussian mixture" (du:349-352):
                                  the z layers live in scope MODIFIED_GAUSSIAN instead of
-                                 SOFTPLUS_GAUSSIAN, same graph */
+                                 SOFTPLUS_GAUSSIAN, same graph; bit 3 (value 8) "full-covariance
+                                 gaussian mixture" (du:347-349): q(z|x,y) and p(z|y) are
+                                 "multivariate gaussian" (du:75-93) -- scope MULTIVARIATE_GAUSSIAN,
+                                 heads LOCATIONS [., L] and SCALES [., L (L + 1) / 2], the lower
+                                 triangle in tfp's fill_triangular order; latent_size <= 64; not
+                                 together with bit 2 */
   float dropout_keep[4];      /* dropout_keep_probabilities (va:245-269, gm:281-301), applied to
                                  the input connections of a dense layer while training
                                  (mu:45-50): [0] h: hidden layers and every parameter head,
@@ -338,6 +343,8 @@ typedef struct scvae_step_args {
   float* stddev_of_p_x_given_z_mean; /* [cells, F] */
   float* cluster_stats;    /* GMVAE: [4, K, L] p_z_means, p_z_variances, q_z_means(sum share),
                               q_z_variances(sum share) */
+  float* cluster_covariances; /* GMVAE, full covariance: [2, K, L, L] p_z_covariances,
+                                 q_z_covariances (sum share) */
   /* [cells, E] extra decoder inputs (required when cfg.decoder_extra > 0), tiled over the
    * samples like t: the decoder's first layer sees [z | decoder_extra] */
   const float* decoder_extra;
@@ -530,7 +537,7 @@ int scvae_gauss_latent_fwd(const float* mu_pre, const float* ls_pre, const float
  * a VAE plan: i (ENCODER/i+1), 16 (POSTERIOR/MU), 17 (POSTERIOR/LOG_SIGMA), 32+i (i-th decoder
  * layer in execution order), 48+j (X_TILDE head j), 51 (X_TILDE/P_K); of a GMVAE plan: 64+i
  * (Y/CATEGORICAL/ENCODER/LAYER_i+1), 80 (Y/CATEGORICAL/LOGITS), i (Z/Q/ENCODER/LAYER_i+1),
- * 16, 17 (Z/Q mean, scale), 24, 25 (Z/P mean, scale), 32+i (X/DECODER/LAYER_i+1), 48+j, 51
+ * 16, 17 (Z/Q mean / locations, scale / scales), 24, 25 (Z/P, the same), 32+i (X/DECODER/LAYER_i+1), 48+j, 51
  * (X/DISTRIBUTION heads); rows of the K passes are stacked, pass-major. */
 int scvae_dropout_apply(const float* in, float* out, int64_t rows, int64_t cols, float keep,
                         uint64_t seed, int32_t site, int32_t accumulate, void* stream);
@@ -621,6 +628,27 @@ int scvae_softplus_gaussian_logprob_pair_bwd(const float* qm, const float* qs, c
                                              const float* gklz, float* dqm, float* dqs,
                                              float* dprior, int64_t K, int64_t S, int64_t B,
                                              int64_t L, void* stream);
+/* The "multivariate gaussian" pair of the full-covariance mixture (du:75-93; gm:2936-3048,
+ * 3272-3292), same calling convention: posterior q(z|x,y=k) = MultivariateNormalTriL(qloc, A) with
+ * qloc [K*B, L] and A = fill_triangular(max(softplus(qscale), FLT_MIN)), qscale [K*B, T],
+ * T = L (L + 1) / 2, L <= 64 (tfp's order: reshape(concat(x[L:], reverse(x)), [L, L]), lower
+ * triangle); prior p(z|y=k) = row k of the Z/P dense layers (Wpl [K, L], bpl [L]; Wps [K, T],
+ * bps [T]) in the same form, P.  z[k,s,b,:] = qloc + A eps[k,s,b,:];
+ * klz[k,s,b] = log q(z) - log p(z|y=k); qvar (optional) [K*B, L] = diag(A A^T); qcov (optional)
+ * [K*B, L, L] = A A^T. */
+int scvae_mvn_tril_logprob_pair_fwd(const float* qloc, const float* qscale, const float* Wpl,
+                                    const float* bpl, const float* Wps, const float* bps,
+                                    const float* eps, float* z, float* klz, float* qvar,
+                                    float* qcov, int64_t K, int64_t S, int64_t B, int64_t L,
+                                    void* stream);
+/* backward: dz [K,S,B,L] and gklz [K,S,B] -> dqloc [K*B, L], dqscale [K*B, T] and the per-cell
+ * prior gradients dprior [K*B, L + T] = (d locations | d scale pre-activations), to be summed
+ * over b for the Z/P layers */
+int scvae_mvn_tril_logprob_pair_bwd(const float* qloc, const float* qscale, const float* Wpl,
+                                    const float* bpl, const float* Wps, const float* bps,
+                                    const float* eps, const float* dz, const float* gklz,
+                                    float* dqloc, float* dqscale, float* dprior, int64_t K,
+                                    int64_t S, int64_t B, int64_t L, void* stream);
 /* q(y|x) = Categorical(logits) (gm:3050-3092): y = softmax(logits) [B, K] and
  * kl_y_cell[b] = KL(q(y|x_b) || p(y)): log K - H[q] for the uniform prior (prior_logits NULL,
  * gm:3242-3254), tfp kl_divergence against softmax(prior_logits) otherwise (gm:3256-3258) */

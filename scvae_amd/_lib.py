@@ -78,6 +78,7 @@ class StepArgs(Structure):
         ("p_x_stddev", c_void_p),
         ("stddev_of_p_x_given_z_mean", c_void_p),
         ("cluster_stats", c_void_p),
+        ("cluster_covariances", c_void_p),
         ("decoder_extra", c_void_p),
         ("dropout_seed", c_uint64),
         ("count_sum", c_void_p),
@@ -284,6 +285,10 @@ SIGNATURES = {
     "scvae_softplus_gaussian_logprob_pair_fwd": (c_int32, [
         c_void_p] * 10 + [c_int64] * 4 + [c_void_p]),
     "scvae_softplus_gaussian_logprob_pair_bwd": (c_int32, [
+        c_void_p] * 12 + [c_int64] * 4 + [c_void_p]),
+    "scvae_mvn_tril_logprob_pair_fwd": (c_int32, [
+        c_void_p] * 11 + [c_int64] * 4 + [c_void_p]),
+    "scvae_mvn_tril_logprob_pair_bwd": (c_int32, [
         c_void_p] * 12 + [c_int64] * 4 + [c_void_p]),
     "scvae_categorical_entropy_kl_fwd": (c_int32, [
         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

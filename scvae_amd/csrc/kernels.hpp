@@ -511,6 +511,23 @@ int gmvae_elbo_bwd(hipStream_t s, const float* ll, const float* klz, const float
 int prior_stats(hipStream_t s, const float* Wpm, const float* bpm, const float* Wps,
                 const float* bps, int K, int L, float* means, float* variances);
 
+// ---- mvn_tril.hip: the latent stage of the full-covariance mixture (du:75-93; L <= 64) ----
+// qloc [K*B, L], qsc [K*B, T] (T = L (L + 1) / 2 scale pre-activations, fill_triangular order);
+// prior = row k of the Z/P layers (Wpl [K, L], bpl [L], Wps [K, T], bps [T]).  qvar (optional)
+// [K*B, L] = diag(A A^T); qcov (optional) [K*B, L, L] = A A^T
+int mvn_tril_fwd(hipStream_t st, const float* qloc, const float* qsc, const float* Wpl,
+                 const float* bpl, const float* Wps, const float* bps, const float* eps, float* z,
+                 float* klz, float* qvar, float* qcov, int K, int S, int B, int L);
+// dqloc [K*B, L], dqsc [K*B, T], dpr [K*B, L + T] = per-cell (d loc_p | d prior scale pre)
+int mvn_tril_bwd(hipStream_t st, const float* qloc, const float* qsc, const float* Wpl,
+                 const float* bpl, const float* Wps, const float* bps, const float* eps,
+                 const float* dz, const float* gklz, float* dqloc, float* dqsc, float* dpr, int K,
+                 int S, int B, int L);
+// means, variances [K, L] = loc_p, diag(P P^T); covariances (optional) [K, L, L] = P P^T
+int mvn_tril_prior_stats(hipStream_t s, const float* Wpl, const float* bpl, const float* Wps,
+                         const float* bps, int K, int L, float* means, float* variances,
+                         float* covariances);
+
 // clip-by-value(+-1) and TF Adam on a flat parameter buffer (va:2742-2759)
 int adam_clip_step(hipStream_t stream, float* theta, float* grad, float* m, float* v, size_t n,
                    float grad_scale, float lr_t, float beta1, float beta2, float epsilon);

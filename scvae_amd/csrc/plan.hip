@@ -1599,9 +1599,22 @@ int scvae_plan_create(const scvae_model_config* cfg, scvae_plan** out) {
   SCVAE_ARG(cfg->linear_factor >= 0 && cfg->linear_factor <= 3);
   SCVAE_ARG(cfg->linear_factor == 0 || cfg->model_type == SCVAE_MODEL_VAE);
   SCVAE_ARG(cfg->decoder_extra == 0 || (cfg->n_hidden > 0 && !(cfg->linear_factor & 2)));
+  if (cfg->model_type == SCVAE_MODEL_VAE && (cfg->latent_mode & 8)) {
+    scvae::set_error("latent_mode bit 3 (full-covariance gaussian mixture) is a GMVAE mode");
+    return -1;
+  }
+  if ((cfg->latent_mode & 8) && (cfg->latent_mode & 4)) {
+    scvae::set_error("latent_mode bits 2 (legacy) and 3 (full covariance) exclude each other");
+    return -1;
+  }
+  if ((cfg->latent_mode & 8) && cfg->latent_size > 64) {
+    scvae::set_error("the full-covariance gaussian mixture supports latent_size <= 64, not %d",
+                     cfg->latent_size);
+    return -1;
+  }
   SCVAE_ARG(cfg->model_type == SCVAE_MODEL_VAE
                 ? (cfg->latent_mode >= 0 && cfg->latent_mode <= 3)
-                : (cfg->latent_mode == 0 || cfg->latent_mode == 4));
+                : (cfg->latent_mode == 0 || cfg->latent_mode == 4 || cfg->latent_mode == 8));
   for (int i = 0; i < 4; ++i) SCVAE_ARG(cfg->dropout_keep[i] >= 0.f && cfg->dropout_keep[i] <= 1.f);
   scvae_plan* p = new scvae_plan();
   p->head_arith = scvae::default_head_arith();
@@ -2403,6 +2416,26 @@ int scvae_softplus_gaussian_logprob_pair_bwd(const float* qm, const float* qs, c
   SCVAE_ARG(Wpm && bpm && Wps && bps && K > 0 && S > 0 && B >= 0 && L > 0);
   return scvae::softplus_gaussian_bwd((hipStream_t)stream, qm, qs, Wpm, bpm, Wps, bps, eps, dz,
                                       gklz, dqm, dqs, dprior, (int)K, (int)S, (int)B, (int)L);
+}
+int scvae_mvn_tril_logprob_pair_fwd(const float* qloc, const float* qscale, const float* Wpl,
+                                    const float* bpl, const float* Wps, const float* bps,
+                                    const float* eps, float* z, float* klz, float* qvar,
+                                    float* qcov, int64_t K, int64_t S, int64_t B, int64_t L,
+                                    void* stream) {
+  SCVAE_ARG(K > 0 && S > 0 && B >= 0 && L > 0 && L <= 64 && K <= 65535 && B <= INT32_MAX &&
+            S <= INT32_MAX);
+  return scvae::mvn_tril_fwd((hipStream_t)stream, qloc, qscale, Wpl, bpl, Wps, bps, eps, z, klz,
+                             qvar, qcov, (int)K, (int)S, (int)B, (int)L);
+}
+int scvae_mvn_tril_logprob_pair_bwd(const float* qloc, const float* qscale, const float* Wpl,
+                                    const float* bpl, const float* Wps, const float* bps,
+                                    const float* eps, const float* dz, const float* gklz,
+                                    float* dqloc, float* dqscale, float* dprior, int64_t K,
+                                    int64_t S, int64_t B, int64_t L, void* stream) {
+  SCVAE_ARG(K > 0 && S > 0 && B >= 0 && L > 0 && L <= 64 && K <= 65535 && B <= INT32_MAX &&
+            S <= INT32_MAX);
+  return scvae::mvn_tril_bwd((hipStream_t)stream, qloc, qscale, Wpl, bpl, Wps, bps, eps, dz, gklz,
+                             dqloc, dqscale, dprior, (int)K, (int)S, (int)B, (int)L);
 }
 int scvae_categorical_entropy_kl_fwd(const float* logits, float* y, float* kl_y_cell, int64_t B,
                                      int64_t K, const float* prior_logits, void* stream) {

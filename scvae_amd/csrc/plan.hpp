@@ -224,6 +224,7 @@ struct scvae_plan {
   float *qm = nullptr, *qs = nullptr, *klz = nullptr, *gklz = nullptr, *dy = nullptr;
   float *dlogits = nullptr, *dqm = nullptr, *dqs = nullptr, *dprior = nullptr;
   float *sum_scratch = nullptr;
+  float* qcov = nullptr;      // full-covariance mixture (latent_mode bit 3): [K*B, L, L] A A^T
 };
 
 namespace scvae {

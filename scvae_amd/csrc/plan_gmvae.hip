@@ -33,11 +33,18 @@ int build_gmvae(scvae_plan* p) {
   }
   // the scope is the upper-cased distribution name (gm:2962-2963, 3013-3014): "softplus gaussian",
   // or its alias "modified gaussian" of the "legacy gaussian mixture" (du:307, 349-352)
-  const std::string dist = (c.latent_mode & 4) ? "MODIFIED_GAUSSIAN" : "SOFTPLUS_GAUSSIAN";
-  p->qmean = L.dense("Z/Q/" + dist + "/MEAN", n_in, Lz, false);
-  p->qscale = L.dense("Z/Q/" + dist + "/SOFTPLUS_SCALE", n_in, Lz, false);
-  p->pmean = L.dense("Z/P/" + dist + "/MEAN", K, Lz, false);
-  p->pscale = L.dense("Z/P/" + dist + "/SOFTPLUS_SCALE", K, Lz, false);
+  // ... or "multivariate gaussian" of the "full-covariance gaussian mixture" (du:75-93, 347-349):
+  // locations [., L] and scales [., L (L + 1) / 2] (the "size function" of du:86)
+  const bool fullcov = (c.latent_mode & 8) != 0;
+  const std::string dist = fullcov ? "MULTIVARIATE_GAUSSIAN"
+                                   : (c.latent_mode & 4) ? "MODIFIED_GAUSSIAN" : "SOFTPLUS_GAUSSIAN";
+  const std::string mean_name = fullcov ? "/LOCATIONS" : "/MEAN";
+  const std::string scale_name = fullcov ? "/SCALES" : "/SOFTPLUS_SCALE";
+  const int Ls = fullcov ? Lz * (Lz + 1) / 2 : Lz;
+  p->qmean = L.dense("Z/Q/" + dist + mean_name, n_in, Lz, false);
+  p->qscale = L.dense("Z/Q/" + dist + scale_name, n_in, Ls, false);
+  p->pmean = L.dense("Z/P/" + dist + mean_name, K, Lz, false);
+  p->pscale = L.dense("Z/P/" + dist + scale_name, K, Ls, false);
   n_in = Lz + c.decoder_extra;   // decoder input [z | batch one-hot | count sum]
   // gm:3135-3146: hidden_sizes[::-1] without reverse_order => LAYER_1.. in execution order
   for (int i = 0; i < c.n_hidden; ++i) {
@@ -89,6 +96,9 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
   if (!dry && workspace_guard_on()) { p->ws_guards.clear(); b.guards = &p->ws_guards; }
   const size_t K = c.n_clusters, B = (size_t)cells, KB = K * B, R = K * B * samples;
   const size_t Lz = c.latent_size, F = c.feature_size;
+  // width of the scale heads: L, or the L (L + 1) / 2 triangle entries of the full-covariance mixture
+  const bool fullcov = (c.latent_mode & 8) != 0;
+  const size_t Ls = (size_t)p->qscale.n_out;
   size_t hmax = Lz > K ? Lz : K;
   size_t gws = 0;
   auto track = [&](size_t M, size_t N, size_t Kd) {
@@ -126,7 +136,7 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
   float* kl_y_cell = b.floats(B);
   float* a0 = b.floats(B * h1z);
   float* qm = b.floats(KB * Lz);
-  float* qs = b.floats(KB * Lz);
+  float* qs = b.floats(KB * Ls);
   float* z = b.floats(R * Lz);
   float* klz = b.floats(R);
   float* gklz = b.floats(R);
@@ -135,8 +145,8 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
   float* dy = b.floats(B * K);
   float* dlogits = b.floats(B * K);
   float* dqm = b.floats(KB * Lz);
-  float* dqs = b.floats(KB * Lz);
-  float* dprior = b.floats(KB * 2 * Lz);
+  float* dqs = b.floats(KB * Ls);
+  float* dprior = b.floats(KB * (Lz + Ls));
   float* kl_cell = b.floats(B + 64);  // rec_cell / scalar sums scratch
   float* pre[3] = {nullptr, nullptr, nullptr};
   for (int j = 0; j < p->P; ++j) pre[j] = b.floats(R * F);
@@ -146,11 +156,14 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
   float* dz = b.floats(R * Lz);
   float* mov = b.floats(B * F);
   float* vom = b.floats(B * F);
-  float* sum_scratch = b.floats(B * hmax + KB * Lz);
+  float* sum_scratch = b.floats(B * hmax + KB * Lz > K * (Lz + Ls) ? B * hmax + KB * Lz
+                                                                   : K * (Lz + Ls));
+  float* qcov = fullcov ? b.floats(KB * Lz * Lz) : nullptr;
   const int hn = c.n_hidden ? c.hidden[c.n_hidden - 1] : (int)F;
   const int h1 = c.n_hidden ? c.hidden[0] : (int)Lz;
   track(B, K, hn); track(hn, K, B); track(B, hn, K);
   track(KB, Lz, hn); track(hn, Lz, KB); track(KB, hn, Lz);
+  if (Ls != Lz) { track(KB, Ls, hn); track(hn, Ls, KB); track(KB, hn, Ls); }
   track(R, F, h1); track(h1, F, R); track(R, h1, F);
   if (c.k_max > 0) {
     const size_t FC = F * (size_t)(c.k_max + 1);
@@ -168,8 +181,14 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
   size_t pmax = col_sum_partial_floats((int)(F > hmax ? F : hmax));
   if (c.k_max > 0) pmax = col_sum_partial_floats((int)(F * (size_t)(c.k_max + 1)));
   {
-    const size_t q = bn_partial_floats((int)K, (int)(hmax > 2 * Lz ? hmax : 2 * Lz));
+    const size_t q = bn_partial_floats((int)K, (int)(hmax > Lz + Ls ? hmax : Lz + Ls));
     if (q > pmax) pmax = q;
+    if (fullcov) {   // column sums of the scale heads' gradient; group sums of A A^T [K*B, L * L]
+      const size_t qc = col_sum_partial_floats((int)Ls);
+      if (qc > pmax) pmax = qc;
+      const size_t qq = bn_partial_floats((int)K, (int)(Lz * Lz));
+      if (qq > pmax) pmax = qq;
+    }
   }
   float* partial = b.floats(pmax);
   float* fused_ws = decoder_fused_train_supported(p->P, h1, 1)
@@ -196,7 +215,7 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
   drop_ws(p->qmean, KB);
   drop_ws(p->qscale, KB);
   { Dense& d = p->pmean; float* q = d.keep > 0.f ? b.floats(K * Lz) : nullptr; if (!dry) d.in_drop = q; }
-  { Dense& d = p->pscale; float* q = d.keep > 0.f ? b.floats(K * Lz) : nullptr; if (!dry) d.in_drop = q; }
+  { Dense& d = p->pscale; float* q = d.keep > 0.f ? b.floats(K * Ls) : nullptr; if (!dry) d.in_drop = q; }
   for (auto& d : p->xdec) drop_ws(d, R);
   for (int j = 0; j < p->P; ++j) drop_ws(p->heads[j], R);
   if (c.k_max > 0) drop_ws(p->head_k, R);
@@ -210,7 +229,7 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
     p->kl_cell = kl_cell;
     for (int j = 0; j < 3; ++j) p->pre[j] = pre[j];
     p->dbuf[0] = d0; p->dbuf[1] = d1; p->dbuf[2] = d2; p->dz = dz;
-    p->mov = mov; p->vom = vom; p->sum_scratch = sum_scratch;
+    p->mov = mov; p->vom = vom; p->sum_scratch = sum_scratch; p->qcov = qcov;
     p->gemm_ws = gemm_ws; p->gemm_ws_bytes = gws; p->partial = partial;
   }
   return b.used;
@@ -295,6 +314,9 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
   const int K = c.n_clusters, B = (int)a->cells, S = a->n_iw * a->n_mc;
   const int KB = K * B, SB = S * B, R = K * SB;
   const int F = c.feature_size, L = c.latent_size;
+  // full-covariance mixture: the scale heads hold the Ls = L (L + 1) / 2 triangle entries
+  const bool fullcov = (c.latent_mode & 8) != 0;
+  const int Ls = p->qscale.n_out;
   const bool training = a->training != 0;
   const int64_t GB = a->global_cells > 0 ? a->global_cells : a->cells;
   const float w = a->warm_up_weight * c.kl_weight;
@@ -391,7 +413,20 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
   const float* hz_m = hz;
   const float* hz_s = hz;
   int ldz_m = ldz, ldz_s = ldz;
-  if (tile) {
+  if (tile && fullcov) {
+    // the scale head is wider than the tile kernels' heads: the last layer's normalisation alone,
+    // then both heads as GEMM launches on its output
+    if (p->zenc.size() > 1) {
+      TileFwdArgs q;
+      q.rows = KB; q.K = p->zenc.back().n_out;
+      TRY(gm_tile_bn_forward(p, s, p->zenc.back(), K, B, p->tc_part[tcur], &q.bn));
+      TRY(tile_forward(s, q));
+    }
+    GEMM(false, false, hz, p->params + p->qmean.w, p->params + p->qmean.b, p->qm, KB, L,
+         p->qmean.n_in, ldz, L, L, ACT_NONE, false);
+    GEMM(false, false, hz, p->params + p->qscale.w, p->params + p->qscale.b, p->qs, KB, Ls,
+         p->qscale.n_in, ldz, Ls, Ls, ACT_NONE, false);
+  } else if (tile) {
     // the two posterior heads on the (here normalised) output of the last q(z|x,y) layer
     TileFwdArgs q;
     q.rows = KB; q.K = p->zenc.back().n_out;
@@ -408,8 +443,8 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
   TRY(dense_input(p, s, p->qscale, hz, ldz, KB, training, &hz_s, &ldz_s));
   GEMM(false, false, hz_m, p->params + p->qmean.w, p->params + p->qmean.b, p->qm, KB, L,
        p->qmean.n_in, ldz_m, L, L, ACT_NONE, false);
-  GEMM(false, false, hz_s, p->params + p->qscale.w, p->params + p->qscale.b, p->qs, KB, L,
-       p->qscale.n_in, ldz_s, L, L, ACT_NONE, false);
+  GEMM(false, false, hz_s, p->params + p->qscale.w, p->params + p->qscale.b, p->qs, KB, Ls,
+       p->qscale.n_in, ldz_s, Ls, Ls, ACT_NONE, false);
   }
   const float* Wpm = p->params + p->pmean.w;
   const float* bpm = p->params + p->pmean.b;
@@ -421,22 +456,39 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
   if (prior_drop) {
     TRY(dropout_scale_rows(s, Wpm, p->pmean.in_drop, K, L, p->pmean.keep, p->drop_seed,
                            p->pmean.site));
-    TRY(dropout_scale_rows(s, Wps, p->pscale.in_drop, K, L, p->pscale.keep, p->drop_seed,
+    TRY(dropout_scale_rows(s, Wps, p->pscale.in_drop, K, Ls, p->pscale.keep, p->drop_seed,
                            p->pscale.site));
     Wpm = p->pmean.in_drop;
     Wps = p->pscale.in_drop;
   }
   float* qvar = a->cluster_stats ? p->dqs : nullptr;  // scratch, free in the forward pass
+  float* qcov = fullcov && a->cluster_covariances ? p->qcov : nullptr;
+  if (fullcov)
+    TRY(mvn_tril_fwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->z, p->klz, qvar, qcov, K, S, B,
+                     L));
+  else
   TRY(softplus_gaussian_fwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->z, p->klz, qvar, K, S,
                             B, L));
   if (a->q_z_mean)  // z_mean = sum_k y_k mean_k (gm:2895-2899)
     TRY(sum_groups(s, p->qm, p->yprob, K, K, B, L, a->q_z_mean));
   if (a->cluster_stats) {
     float* cs = a->cluster_stats;
+    if (fullcov)
+      TRY(mvn_tril_prior_stats(s, Wpm, bpm, Wps, bps, K, L, cs, cs + (size_t)K * L, nullptr));
+    else
     TRY(prior_stats(s, Wpm, bpm, Wps, bps, K, L, cs, cs + (size_t)K * L));
     // q_z_means / q_z_variances: this rank's share of the batch means (gm:2884-2887)
     TRY(group_col_sum(s, p->qm, L, B, K, L, inv_gb, cs + 2 * (size_t)K * L, p->partial));
     TRY(group_col_sum(s, qvar, L, B, K, L, inv_gb, cs + 3 * (size_t)K * L, p->partial));
+  }
+  if (qcov) {
+    // p_z_covariances = P P^T; q_z_covariances: this rank's share of the batch mean of A A^T
+    // (gm:2889-2893)
+    float* cc = a->cluster_covariances;
+    const size_t KLL = (size_t)K * L * L;
+    TRY(mvn_tril_prior_stats(s, Wpm, bpm, Wps, bps, K, L, p->sum_scratch,
+                             p->sum_scratch + (size_t)K * L, cc));
+    TRY(group_col_sum(s, qcov, L * L, B, K, L * L, inv_gb, cc + KLL, p->partial));
   }
 
   // ---------------- decoder p(x|z_k), all k (gm:3094-3221) ----------------
@@ -681,28 +733,33 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
   if (E > 0 && !p->xdec.empty()) TRY(slice_cols(s, p->dzcat, L + E, L, (size_t)R, p->dz));
 
   // ---------------- backward: latent, prior, q(z|x,y) ----------------
+  if (fullcov)
+    TRY(mvn_tril_bwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->dz, p->gklz, p->dqm, p->dqs,
+                     p->dprior, K, S, B, L));
+  else
   TRY(softplus_gaussian_bwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->dz, p->gklz, p->dqm,
                             p->dqs, p->dprior, K, S, B, L));
   // prior dense layers on the one-hot: dW[k,:] = sum_b, db = sum_k dW[k,:]
-  TRY(group_col_sum(s, p->dprior, 2 * L, B, K, 2 * L, 1.f, p->sum_scratch, p->partial));
+  const int LP = L + Ls;   // row of dprior: (d pm | d ps)
+  TRY(group_col_sum(s, p->dprior, LP, B, K, LP, 1.f, p->sum_scratch, p->partial));
   {
-    // sum_scratch: [K, 2L] = (d pm | d ps) rows; scatter into the two weight matrices
+    // sum_scratch: [K, L + Ls] = (d pm | d ps) rows; scatter into the two weight matrices
     float* dWpm = p->grads + p->pmean.w;
     float* dWps = p->grads + p->pscale.w;
-    TRY(hipMemcpy2DAsync(dWpm, L * sizeof(float), p->sum_scratch, 2 * L * sizeof(float),
+    TRY(hipMemcpy2DAsync(dWpm, L * sizeof(float), p->sum_scratch, LP * sizeof(float),
                          L * sizeof(float), K, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -2);
-    TRY(hipMemcpy2DAsync(dWps, L * sizeof(float), p->sum_scratch + L, 2 * L * sizeof(float),
-                         L * sizeof(float), K, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -2);
+    TRY(hipMemcpy2DAsync(dWps, Ls * sizeof(float), p->sum_scratch + L, LP * sizeof(float),
+                         Ls * sizeof(float), K, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -2);
     TRY(col_sum(s, dWpm, L, K, L, p->grads + p->pmean.b, 1.f, 0, nullptr));
-    TRY(col_sum(s, dWps, L, K, L, p->grads + p->pscale.b, 1.f, 0, nullptr));
+    TRY(col_sum(s, dWps, Ls, K, Ls, p->grads + p->pscale.b, 1.f, 0, nullptr));
     if (prior_drop) {   // the weights saw the masked one-hot; the biases did not
       TRY(dropout_scale_rows(s, dWpm, dWpm, K, L, p->pmean.keep, p->drop_seed, p->pmean.site));
-      TRY(dropout_scale_rows(s, dWps, dWps, K, L, p->pscale.keep, p->drop_seed, p->pscale.site));
+      TRY(dropout_scale_rows(s, dWps, dWps, K, Ls, p->pscale.keep, p->drop_seed, p->pscale.site));
     }
   }
   float* dh = p->dbuf[0];
   float* dh_alt = p->dbuf[1];
-  if (tile) {
+  if (tile && !fullcov) {
     // the two posterior heads: dW, db of both, dh of the last q(z|x,y) layer and (where that
     // layer belongs to the chain) its chunk sums
     Dense& last = p->zenc.back();
@@ -727,18 +784,25 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     pending.job[j0 + 2] = {q.up[0].db_slab, p->grads + p->qmean.b, L, G};
     pending.job[j0 + 3] = {q.up[1].db_slab, p->grads + p->qscale.b, L, G};
     pending.n_jobs = j0 + 4;
-  } else
+  } else {
   for (int q = 0; q < 2; ++q) {
     Dense& hd = q == 0 ? p->qmean : p->qscale;
     const float* dpre = q == 0 ? p->dqm : p->dqs;
     const float* hq = q == 0 ? hz_m : hz_s;   // the (dropped-out) input of that layer
     const bool drop = hd.keep > 0.f;
-    GEMM(true, false, hq, dpre, nullptr, p->grads + hd.w, hd.n_in, L, KB, hd.n_in, L, L, ACT_NONE,
+    const int N = hd.n_out;   // L, or Ls for the scales of the full-covariance mixture
+    GEMM(true, false, hq, dpre, nullptr, p->grads + hd.w, hd.n_in, N, KB, hd.n_in, N, N, ACT_NONE,
          false);
-    TRY(col_sum(s, dpre, L, KB, L, p->grads + hd.b, 1.f, 0, p->partial));
-    GEMM(false, true, dpre, p->params + hd.w, nullptr, drop ? dh_alt : dh, KB, hd.n_in, L, L, L,
+    TRY(col_sum(s, dpre, N, KB, N, p->grads + hd.b, 1.f, 0, p->partial));
+    GEMM(false, true, dpre, p->params + hd.w, nullptr, drop ? dh_alt : dh, KB, hd.n_in, N, N, N,
          hd.n_in, ACT_NONE, !drop && q > 0);
     if (drop) TRY(dense_input_backward(p, s, hd, dh_alt, dh, KB, q > 0));
+  }
+  // (full covariance on the tile chain: the heads ran as GEMMs; the chain's next kernel wants the
+  //  chunk sums of the last q(z|x,y) layer's batch-norm backward, as the decoder's top layer)
+  if (tile && p->zenc.size() > 1)
+    TRY(tile_backward_stats(s, dh, gm_tile_bn(p, p->zenc.back(), K, B, nullptr, p->tc_spart[sp]),
+                            KB, p->zenc.back().n_out));
   }
   for (int i = (int)p->zenc.size() - 1; i >= 0; --i) {
     Dense& d = p->zenc[i];

@@ -11,7 +11,8 @@ their zero-inflated forms) are executed by the HIP kernels of
 directly from the head pre-activations (``scvae_plan_step``), this registry is
 the element-wise plug-in view of them.  The Gaussian entries describe the
 latent distributions (``gaussian`` for the VAE posterior/prior, ``softplus
-gaussian`` for the GMVAE) whose arithmetic is fused into the latent kernels.
+gaussian`` and ``multivariate gaussian`` for the GMVAE) whose arithmetic is
+fused into the latent kernels.
 """
 
 import ctypes
@@ -154,6 +155,49 @@ class NormalDistribution:
             shape, device=self.loc.device, dtype=self.loc.dtype)
 
 
+def fill_triangular(x):
+    """``tfp.distributions.fill_triangular``: the last axis of ``x`` (length
+    ``L (L + 1) / 2``) as a lower-triangular ``[..., L, L]`` matrix in tfp's
+    order -- ``reshape(concat(x[L:], reverse(x)), [L, L])``, lower triangle
+    kept: ``[1, 2, 3, 4, 5, 6]`` gives ``[[4, 0, 0], [6, 5, 0], [3, 2, 1]]``."""
+    T = x.shape[-1]
+    L = int((math.sqrt(8 * T + 1) - 1) / 2)
+    if L * (L + 1) // 2 != T:
+        raise ValueError(
+            "{} values do not fill a triangular matrix.".format(T))
+    y = torch.cat([x[..., L:], torch.flip(x, dims=(-1,))], dim=-1)
+    return torch.tril(y.reshape(x.shape[:-1] + (L, L)))
+
+
+class MultivariateNormalTriL:
+    """``MultivariateNormalTriL(loc, scale_tril)`` of the reference
+    (distributions/multivariate_normal.py:90-149): the element-wise plug-in
+    view; inside a step the arithmetic is csrc/mvn_tril.hip."""
+
+    def __init__(self, loc, scale_tril):
+        self.loc, self.scale_tril = loc, scale_tril
+        self._distribution = torch.distributions.MultivariateNormal(
+            loc=loc, scale_tril=scale_tril, validate_args=False)
+
+    def mean(self):
+        return self.loc
+
+    def covariance(self):
+        return self.scale_tril @ self.scale_tril.transpose(-1, -2)
+
+    def variance(self):
+        return (self.scale_tril ** 2).sum(dim=-1)
+
+    def stddev(self):
+        return torch.sqrt(self.variance())
+
+    def log_prob(self, z):
+        return self._distribution.log_prob(z)
+
+    def sample(self, sample_shape=()):
+        return self._distribution.sample(tuple(sample_shape))
+
+
 DISTRIBUTIONS = {
     "gaussian": {
         "parameters": {
@@ -188,6 +232,24 @@ DISTRIBUTIONS = {
             loc=theta["mean"],
             scale=torch.sqrt(torch.nn.functional.softplus(
                 theta["softplus_scale"])))
+    },
+    "multivariate gaussian": {
+        "parameters": {
+            "locations": {
+                "support": [-numpy.inf, numpy.inf],
+                "activation function": identity,
+                "initial value": torch.zeros
+            },
+            "scales": {
+                "support": [0, numpy.inf],
+                "activation function": softplus,
+                "initial value": torch.ones,
+                "size function": lambda m: int(m * (m + 1) / 2)
+            }
+        },
+        "class": lambda theta: MultivariateNormalTriL(
+            loc=theta["locations"],
+            scale_tril=fill_triangular(theta["scales"]))
     },
     "categorical": {
         "parameters": {
@@ -303,7 +365,7 @@ DISTRIBUTIONS["constrained poisson"] = {
 
 #: reference likelihoods that this build does not provide kernels for
 UNSUPPORTED_DISTRIBUTIONS = (
-    "multivariate gaussian", "gaussian mixture", "log-normal",
+    "gaussian mixture", "log-normal",
     "exponentially_modified_gaussian", "gamma", "lomax")
 
 LATENT_DISTRIBUTIONS = {
@@ -333,6 +395,10 @@ GAUSSIAN_MIXTURE_DISTRIBUTIONS = {
     "gaussian mixture": {
         "z prior": "softplus gaussian",
         "z posterior": "softplus gaussian"
+    },
+    "full-covariance gaussian mixture": {
+        "z prior": "multivariate gaussian",
+        "z posterior": "multivariate gaussian"
     },
     "legacy gaussian mixture": {
         "z prior": "modified gaussian",

@@ -105,7 +105,8 @@ class Engine:
             | (2 if generative_architecture.upper() == "LFM" else 0))
         if latent_distribution not in (
                 "gaussian", "unit-variance gaussian", "gaussian mixture",
-                "legacy gaussian mixture"):
+                "legacy gaussian mixture",
+                "full-covariance gaussian mixture"):
             raise ValueError("Latent distribution `{}`.".format(
                 latent_distribution))
         self.latent_distribution = latent_distribution
@@ -114,6 +115,17 @@ class Engine:
         if model_type == "GMVAE":
             if latent_distribution == "legacy gaussian mixture":
                 cfg.latent_mode = 4
+            elif latent_distribution == "full-covariance gaussian mixture":
+                # one wave per (cluster, cell), a lane per row of the triangle
+                if self.latent_size > 64:
+                    raise ValueError(
+                        "The full-covariance Gaussian mixture supports a "
+                        "latent size of at most 64, not {}.".format(
+                            self.latent_size))
+                cfg.latent_mode = 8
+        elif latent_distribution == "full-covariance gaussian mixture":
+            raise ValueError("Latent distribution `{}` is a GMVAE one.".format(
+                latent_distribution))
         else:
             cfg.latent_mode = (
                 (0 if self.analytical_kl_term else 1)

@@ -1252,7 +1252,7 @@ class ModelBase:
                     numpy.atleast_1d(evaluation["kl_divergence_neurons"])):
                 scalars["kl_divergence_neurons/{}".format(i)] = value
         if prior is not None:
-            probabilities, means, variances = prior
+            probabilities, means, variances = prior[:3]
             for k in range(len(probabilities)):
                 scalars["prior/cluster_{}/probability".format(k)] = (
                     probabilities[k])

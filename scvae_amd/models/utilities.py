@@ -547,6 +547,12 @@ def load_centroids(model, data_set_kinds="all", run_id=None,
                         "prior/cluster_{}/mean/dimension_{}".format(k, l)]
                     covariances[e, k, l, l] = s[
                         "prior/cluster_{}/variance/dimension_{}".format(k, l)]
+                    # the full-covariance mixture logs every entry (gm:1406-1417)
+                    for l_ in range(L):
+                        tag = "prior/cluster_{}/covariance/dimension_{}_{}".format(
+                            k, l, l_)
+                        if tag in s:
+                            covariances[e, k, l, l_] = s[tag]
         sets[kind] = {"prior": {"probabilities": probabilities,
                                 "means": means,
                                 "covariance_matrices": covariances}}
