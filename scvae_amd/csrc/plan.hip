@@ -1,4 +1,6 @@
-// Host-side execution plan of the VAE + the exported C ABI (see plan.hpp).
+// Host-side execution plan of the VAE, the step stages it shares with the GMVAE's plan
+// (plan_gmvae.hip) and the plan's entries of the C ABI (see plan.hpp; the stand-alone entries are
+// in abi_ops.hip).
 #include <mutex>
 #include <vector>
 #include "plan.hpp"
@@ -95,6 +97,11 @@ static int build_vae(scvae_plan* p) {
   return 0;
 }
 
+// SCVAE_TILE_CHAIN=0: no step takes the tile chain (A/B against the launches)
+bool tile_chain_enabled() {
+  static const bool on = [] { const char* e = getenv("SCVAE_TILE_CHAIN"); return !(e && e[0] == '0'); }();
+  return on;
+}
 bool count_tiles_enabled() {
   static const bool on = [] { const char* e = getenv("SCVAE_COUNT_TILES"); return !(e && e[0] == '0'); }();
   return on;
@@ -371,7 +378,7 @@ int dense_affine(scvae_plan* p, hipStream_t s, Dense& d, const float* in, int ld
         (p->use_bn_cols >= 2 || bn_cols_pays(rows)) && bn_cols_layout_ok(d.a, N) && bn_cols_layout_ok(d.h, N) &&
         bn_cols_layout_ok(p->params + d.beta, 4) && bn_cols_layout_ok(mean, N))
       return bn_fwd_cols(s, d.a, N, rows, N, p->params + d.beta, relu ? 1 : 0, d.h, N, mean, var);
-    if ((rc = bn_stats(s, d.a, N, rpg, groups, N, mean, var, p->partial))) return rc;
+    TRY(bn_stats(s, d.a, N, rpg, groups, N, mean, var, p->partial));
     if (p->sync) {
       // statistics of the global minibatch (sync batch norm); groups == 1 on this path
       if (p->sync(p->sync_user, d.stats, 2 * (int64_t)groups * N, 1, rpg)) {
@@ -379,9 +386,8 @@ int dense_affine(scvae_plan* p, hipStream_t s, Dense& d, const float* in, int ld
         return -2;
       }
     }
-    if ((rc = bn_apply(s, d.a, N, mean, var, N, p->params + d.beta, d.h, N, rpg, groups, N,
-                       relu ? 1 : 0)))
-      return rc;
+    TRY(bn_apply(s, d.a, N, mean, var, N, p->params + d.beta, d.h, N, rpg, groups, N,
+                 relu ? 1 : 0));
     return 0;
   }
   return bn_apply(s, d.a, N, p->moving + d.mov_mean, p->moving + d.mov_var, 0, p->params + d.beta,
@@ -395,7 +401,6 @@ int dense_backward_activation(scvae_plan* p, hipStream_t s, Dense& d, int rows, 
                               bool relu, const float* dh, float* scratch,
                               int64_t global_rows_per_group, const float** da_out) {
   const int N = d.n_out;
-  int rc;
   *da_out = dh;
   if (d.bn) {
     const int rpg = rows / groups;
@@ -409,32 +414,29 @@ int dense_backward_activation(scvae_plan* p, hipStream_t s, Dense& d, int rows, 
         bn_cols_layout_ok(p->grads + d.beta, 4) && bn_cols_layout_ok(p->moving + d.mov_mean, 4) &&
         bn_cols_layout_ok(p->moving + d.mov_var, 4)) {
       // sums + dbeta + moving averages + da in one launch
-      if ((rc = bn_bwd_cols(s, dh, N, d.h, N, d.a, N, mean, var, rows, N, relu ? 1 : 0, scratch, N,
-                            s1, s2, p->grads + d.beta, p->moving + d.mov_mean,
-                            p->moving + d.mov_var)))
-        return rc;
+      TRY(bn_bwd_cols(s, dh, N, d.h, N, d.a, N, mean, var, rows, N, relu ? 1 : 0, scratch, N,
+                      s1, s2, p->grads + d.beta, p->moving + d.mov_mean,
+                      p->moving + d.mov_var));
       *da_out = scratch;
       return 0;
     }
     // the statistics launch also writes dbeta (sum over this rank's rows of dA, taken before s1
     // becomes a global sum) and updates the layer's moving averages from the (possibly synced)
     // batch statistics of the forward pass
-    if ((rc = bn_bwd_stats(s, dh, N, d.h, N, d.a, N, mean, var, rpg, groups, N, relu ? 1 : 0, s1,
-                           s2, p->partial, p->grads + d.beta, p->moving + d.mov_mean,
-                           p->moving + d.mov_var, global_rows_per_group)))
-      return rc;
+    TRY(bn_bwd_stats(s, dh, N, d.h, N, d.a, N, mean, var, rpg, groups, N, relu ? 1 : 0, s1,
+                     s2, p->partial, p->grads + d.beta, p->moving + d.mov_mean,
+                     p->moving + d.mov_var, global_rows_per_group));
     if (p->sync) {
       if (p->sync(p->sync_user, s1, 2 * (int64_t)groups * N, 0, rpg)) {
         set_error("batch-norm backward sync hook failed");
         return -2;
       }
     }
-    if ((rc = bn_bwd_apply(s, dh, N, d.h, N, d.a, N, mean, var, s1, s2, rpg, groups, N,
-                           relu ? 1 : 0, 1.f / (float)global_rows_per_group, scratch, N)))
-      return rc;
+    TRY(bn_bwd_apply(s, dh, N, d.h, N, d.a, N, mean, var, s1, s2, rpg, groups, N,
+                     relu ? 1 : 0, 1.f / (float)global_rows_per_group, scratch, N));
     *da_out = scratch;
   } else if (relu) {
-    if ((rc = relu_bwd(s, dh, d.h, scratch, (size_t)rows * N))) return rc;
+    TRY(relu_bwd(s, dh, d.h, scratch, (size_t)rows * N));
     *da_out = scratch;
   }
   return 0;
@@ -445,12 +447,10 @@ int dense_backward(scvae_plan* p, hipStream_t s, Dense& d, const float* in, int 
                    int groups, bool relu, const float* dh, float* scratch, float* d_in,
                    bool accumulate_d_in, int64_t global_rows_per_group) {
   const int N = d.n_out;
-  int rc;
   const float* da = nullptr;
   if (d.keep > 0.f) { in = d.in_drop; ld_in = d.n_in; }   // what the forward GEMM read
-  if ((rc = dense_backward_activation(p, s, d, rows, groups, relu, dh, scratch,
-                                      global_rows_per_group, &da)))
-    return rc;
+  TRY(dense_backward_activation(p, s, d, rows, groups, relu, dh, scratch,
+                                global_rows_per_group, &da));
   if (p->sync && p->early_reduce_layer == &d) {
     // everything between ENCODER/1 and the likelihood heads (announced after the head kernel)
     if (p->sync(p->sync_user, p->grads + p->early_reduce_start,
@@ -459,23 +459,21 @@ int dense_backward(scvae_plan* p, hipStream_t s, Dense& d, const float* in, int 
       return -2;
     }
   }
-  if ((rc = plan_gemm(p, s, true, false, in, da, nullptr, p->grads + d.w, d.n_in, N, rows, ld_in, N,
-                      N, ACT_NONE, false)))
-    return rc;
+  TRY(plan_gemm(p, s, true, false, in, da, nullptr, p->grads + d.w, d.n_in, N, rows, ld_in, N,
+                N, ACT_NONE, false));
   // bias of a batch-normalised layer: the batch mean is subtracted again, its gradient is
   // identically zero (the reference computes rounding noise there); the slot was zeroed at bind
   if (!d.bn)
-    if ((rc = col_sum(s, da, N, rows, N, p->grads + d.b, 1.f, 0, p->partial))) return rc;
+    TRY(col_sum(s, da, N, rows, N, p->grads + d.b, 1.f, 0, p->partial));
   if (d_in) {
     if (d.keep > 0.f && accumulate_d_in) {
       set_error("dense_backward: accumulation into a dropped-out input");
       return -1;
     }
-    if ((rc = gemm(s, false, true, da, p->params + d.w, nullptr, d_in, rows, d.n_in, N, N, N,
-                   d.n_in, ACT_NONE, accumulate_d_in, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
+    TRY(gemm(s, false, true, da, p->params + d.w, nullptr, d_in, rows, d.n_in, N, N, N,
+             d.n_in, ACT_NONE, accumulate_d_in, p->gemm_ws, p->gemm_ws_bytes));
     if (d.keep > 0.f)
-      if ((rc = dense_input_backward(p, s, d, d_in, d_in, rows, false))) return rc;
+      TRY(dense_input_backward(p, s, d, d_in, d_in, rows, false));
   }
   return 0;
 }
@@ -519,20 +517,18 @@ namespace scvae {
 int heads_forward(scvae_plan* p, hipStream_t s, const float* dch, int ld, int R, bool training,
                   const float* (&head_in)[4]) {
   const int F = p->cfg.feature_size, KM = p->cfg.k_max, FC = F * (KM + 1);
-  int rc, ldh = ld;
+  int ldh = ld;
   for (int j = 0; j < p->P; ++j) {
     Dense& hd = p->heads[j];
-    if ((rc = dense_input(p, s, hd, dch, ld, R, training, &head_in[j], &ldh))) return rc;
-    if ((rc = gemm(s, false, false, head_in[j], p->params + hd.w, p->params + hd.b, p->pre[j], R, F,
-                   hd.n_in, ldh, F, F, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
+    TRY(dense_input(p, s, hd, dch, ld, R, training, &head_in[j], &ldh));
+    TRY(gemm(s, false, false, head_in[j], p->params + hd.w, p->params + hd.b, p->pre[j], R, F,
+             hd.n_in, ldh, F, F, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes));
   }
   if (KM > 0) {
     Dense& hk = p->head_k;
-    if ((rc = dense_input(p, s, hk, dch, ld, R, training, &head_in[3], &ldh))) return rc;
-    if ((rc = gemm(s, false, false, head_in[3], p->params + hk.w, p->params + hk.b, p->pre_k, R, FC,
-                   hk.n_in, ldh, FC, FC, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
+    TRY(dense_input(p, s, hk, dch, ld, R, training, &head_in[3], &ldh));
+    TRY(gemm(s, false, false, head_in[3], p->params + hk.w, p->params + hk.b, p->pre_k, R, FC,
+             hk.n_in, ldh, FC, FC, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes));
   }
   return 0;
 }
@@ -543,22 +539,19 @@ int heads_backward(scvae_plan* p, hipStream_t s, const float* const (&head_in)[4
                    bool head_drop, float* dd, float* scratch) {
   const int F = p->cfg.feature_size, KM = p->cfg.k_max, FC = F * (KM + 1);
   const int h1 = p->heads[0].n_in;
-  int rc;
   auto one = [&](Dense& hd, const float* in, float* G, int N, bool first) -> int {
-    if ((rc = gemm(s, true, false, in, G, nullptr, p->grads + hd.w, h1, N, R, h1, N, N, ACT_NONE,
-                   false, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
-    if ((rc = col_sum(s, G, N, R, N, p->grads + hd.b, 1.f, 0, p->partial))) return rc;
-    if ((rc = gemm(s, false, true, G, p->params + hd.w, nullptr, head_drop ? scratch : dd, R, h1,
-                   N, N, N, h1, ACT_NONE, !head_drop && !first, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
+    TRY(gemm(s, true, false, in, G, nullptr, p->grads + hd.w, h1, N, R, h1, N, N, ACT_NONE,
+             false, p->gemm_ws, p->gemm_ws_bytes));
+    TRY(col_sum(s, G, N, R, N, p->grads + hd.b, 1.f, 0, p->partial));
+    TRY(gemm(s, false, true, G, p->params + hd.w, nullptr, head_drop ? scratch : dd, R, h1,
+             N, N, N, h1, ACT_NONE, !head_drop && !first, p->gemm_ws, p->gemm_ws_bytes));
     if (head_drop) return dense_input_backward(p, s, hd, scratch, dd, R, !first);
     return 0;
   };
   for (int j = 0; j < p->P; ++j)
-    if ((rc = one(p->heads[j], head_in[j], p->pre[j], F, j == 0))) return rc;
+    TRY(one(p->heads[j], head_in[j], p->pre[j], F, j == 0));
   if (KM > 0)   // the P_K head, same three products on [rows, F * (K + 1)]
-    if ((rc = one(p->head_k, head_in[3], p->pre_k, FC, false))) return rc;
+    TRY(one(p->head_k, head_in[3], p->pre_k, FC, false));
   return 0;
 }
 
@@ -571,10 +564,10 @@ bool heads_fused_dropout_ok(scvae_plan* p, int n_iw) {
 }
 int heads_dropout_inputs(scvae_plan* p, hipStream_t s, const float* dch, int ld, int R,
                          HeadDropout* out) {
-  int rc, ldh = ld;
+  int ldh = ld;
   for (int j = 0; j < p->P; ++j) {
     Dense& hd = p->heads[j];
-    if ((rc = dense_input(p, s, hd, dch, ld, R, true, &out->d[j], &ldh))) return rc;
+    TRY(dense_input(p, s, hd, dch, ld, R, true, &out->d[j], &ldh));
     out->site[j] = hd.site;
   }
   out->keep = p->heads[0].keep;
@@ -598,8 +591,7 @@ HeadParams head_params(scvae_plan* p) {
 // ---- large training minibatches: one launch per hidden layer and direction (tilechain.hip) ----
 static bool tile_chain_ok(const scvae_plan* p, int B, int S, bool training) {
   const scvae_model_config& c = p->cfg;
-  static const bool env_on = [] { const char* e = getenv("SCVAE_TILE_CHAIN"); return !(e && e[0] == '0'); }();
-  if (!env_on || !p->use_tile_chain || !training) return false;
+  if (!tile_chain_enabled() || !p->use_tile_chain || !training) return false;
   if (!c.batch_norm || p->enc.empty() || p->dec.empty()) return false;
   if (c.latent_mode != 0 || c.decoder_extra != 0 || c.latent_size > 128) return false;
   if ((int64_t)B * S <= 128) return false;      // (the mid-chain kernels' regime)
@@ -631,15 +623,22 @@ static bool tile_resident_ok(const scvae_plan* p, int R) {
   if (n_dec + 4 + (n_enc - 1) > TC_MAX_JOBS) return false;                  // dW / db slab jobs
   return true;
 }
-// the batch norm of layer d as the tile kernels see it
-static TileBN tile_bn(scvae_plan* p, Dense& d, const float* part, int chunks, int chunk,
-                      float* part_out) {
+// the batch norm of layer d as the tile kernels see it.  group_rows == 0 (the VAE): one group,
+// statistics [N], the chunks as given (bn_stats_partial chooses the first layer's, later layers
+// have 64 rows and a ragged tail).  group_rows > 0 (the GMVAE's K stacked passes): `groups`
+// groups of group_rows rows -- whole 64-row tiles -- with their own statistics [groups][N]
+TileBN tile_bn(scvae_plan* p, Dense& d, int groups, int group_rows, const float* part, int chunks,
+               int chunk, float* part_out) {
   TileBN t;
-  const int N = d.n_out;
+  const size_t GN = (size_t)groups * d.n_out;
   t.a = d.a; t.h = d.h; t.beta = p->params + d.beta;
-  t.mean = d.stats; t.var = d.stats + N;
-  t.s1 = d.stats + 2 * (size_t)N; t.s2 = d.stats + 3 * (size_t)N;
+  t.mean = d.stats; t.var = d.stats + GN;
+  t.s1 = d.stats + 2 * GN; t.s2 = d.stats + 3 * GN;
   t.part = part; t.chunks = chunks; t.chunk = chunk; t.part_out = part_out;
+  if (group_rows > 0) {
+    t.group_tiles = group_rows / 64; t.groups = groups;
+    t.chunks = groups * t.group_tiles; t.chunk = 64;
+  }
   t.dbeta = p->grads ? p->grads + d.beta : nullptr;
   t.mov_mean = p->moving + d.mov_mean; t.mov_var = p->moving + d.mov_var;
   return t;
@@ -700,43 +699,209 @@ static int eval_chain(scvae_plan* p, const scvae_step_args* a, hipStream_t s, in
   return eval_mlp(s, q);
 }
 
-// Data-parallel steps (scvae_plan_set_sync): the statistics of layer d over the GLOBAL minibatch
-// before the tile kernel that consumes them -- this rank's chunks merged into d.stats, the hook
-// (kind 1: all-gather + Chan merge over the ranks), and a TileBN that hands them over as given
-// (part == nullptr).  Without a hook: the chunks themselves, merged by the consuming kernel.
-static int tile_bn_forward(scvae_plan* p, hipStream_t s, Dense& d, const float* part, int chunks,
-                           int chunk, int rows, TileBN* out) {
+// The batch norm of layer d for the tile kernel that CONSUMES its forward statistics.  Single
+// process: the chunk statistics `part` themselves, merged by that kernel.  Data parallel
+// (scvae_plan_set_sync): the statistics are those of the GLOBAL minibatch -- this rank's chunks
+// merged into d.stats (per group), the hook (kind 1: all-gather + Chan merge over the ranks; the
+// groups' statistics in ONE collective), and a TileBN that hands them over as given
+// (part == nullptr).
+int tile_bn_forward(scvae_plan* p, hipStream_t s, Dense& d, int groups, int group_rows,
+                    const float* part, int chunks, int chunk, int rows, TileBN* out) {
   if (!p->sync) {
-    *out = tile_bn(p, d, part, chunks, chunk, nullptr);
+    *out = tile_bn(p, d, groups, group_rows, part, chunks, chunk, nullptr);
     return 0;
   }
   const int N = d.n_out;
-  int rc = tile_stats_merge(s, part, chunks, chunk, rows, N, d.stats, d.stats + N);
-  if (rc) return rc;
-  if (p->sync(p->sync_user, d.stats, 2 * (int64_t)N, 1, rows)) {
+  if (group_rows > 0) { chunks = group_rows / 64; chunk = 64; rows = group_rows; }   // (per group)
+  TRY(tile_stats_merge(s, part, chunks, chunk, rows, N, d.stats, d.stats + (size_t)groups * N,
+                       groups));
+  if (p->sync(p->sync_user, d.stats, 2 * (int64_t)groups * N, 1, rows)) {
     set_error("batch-norm sync hook failed");
     return -2;
   }
-  *out = tile_bn(p, d, nullptr, 0, 0, nullptr);
+  *out = tile_bn(p, d, groups, group_rows, nullptr, 0, 0, nullptr);
   return 0;
 }
-// ... and the sums of the backward pass (kind 0: all-reduce); dbeta (this rank's rows) and the
-// moving averages are written by the merge
-static int tile_bn_backward(scvae_plan* p, hipStream_t s, Dense& d, const float* part, int chunks,
-                            int rows, float bessel, TileBN* out) {
+// ... and for the kernel that consumes the sums of its backward pass (kind 0: all-reduce; s1, s2
+// behind mean / var); dbeta (this rank's rows) and the moving averages are written by the merge
+int tile_bn_backward(scvae_plan* p, hipStream_t s, Dense& d, int groups, int group_rows,
+                     const float* part, int rows, float bessel, TileBN* out) {
+  const int per_group = group_rows > 0 ? group_rows : rows;
+  const int chunks = (per_group + 63) / 64;
   if (!p->sync) {
-    *out = tile_bn(p, d, part, chunks, 64, nullptr);
+    *out = tile_bn(p, d, groups, group_rows, part, chunks, 64, nullptr);
     return 0;
   }
   const int N = d.n_out;
-  TileBN t = tile_bn(p, d, nullptr, 0, 0, nullptr);
-  int rc = tile_sums_merge(s, part, chunks, N, t, bessel);
-  if (rc) return rc;
-  if (p->sync(p->sync_user, t.s1, 2 * (int64_t)N, 0, rows)) {   // (rows as the launch chain passes them)
+  TileBN t = tile_bn(p, d, groups, group_rows, nullptr, 0, 0, nullptr);
+  TRY(tile_sums_merge(s, part, chunks, N, t, bessel, groups));
+  if (p->sync(p->sync_user, t.s1, 2 * (int64_t)groups * N, 0, per_group)) {   // (rows as the launch chain passes them)
     set_error("batch-norm backward sync hook failed");
     return -2;
   }
   *out = t;
+  return 0;
+}
+
+// ---- the stages of a tile chain (TileChain, plan.hpp), shared by vae_step and gmvae_step ----
+// A tile stage runs as its own launch, or -- a recording chain -- joins the launch being recorded;
+// that launch goes out where a stage needs every tile's statistics (segments) or at the end of
+// the pass (resident).
+int tile_fwd_flush(TileChain& tc) {
+  TileChainFwdArgs& cf = tc.cf;
+  if (cf.n == 0) return 0;
+  int r;
+  if (cf.n == 1 && cf.kind[0] == TCS_TILE) {
+    r = tile_forward(tc.s, cf.f[0]);
+  } else if (cf.n == 1) {
+    const TileLatent& t = cf.lat;
+    r = gauss_latent_fwd(tc.s, t.mu_pre, t.ls_pre, t.eps, t.z, t.kl_elem, t.kl_cell, nullptr, t.S,
+                         t.B, t.L, 0);
+  } else {
+    cf.bar = tc.p->mid_bar; cf.bar_base = tc.p->mid_bar_count;
+    unsigned advance = 0;
+    r = tile_chain_forward(tc.s, cf, tc.tiles, &advance);
+    tc.p->mid_bar_count += advance;
+  }
+  cf.n = 0; tc.cf_tiles = 0;
+  return r;
+}
+int tile_fwd_stage(TileChain& tc, const TileFwdArgs& q, int sync_after) {
+  if (!tc.record) return tile_forward(tc.s, q);
+  TileChainFwdArgs& cf = tc.cf;
+  SCVAE_ARG(cf.n < TCR_MAX_STAGES && tc.cf_tiles < TCR_MAX_TILES);
+  cf.f[tc.cf_tiles] = q;
+  cf.kind[cf.n] = TCS_TILE; cf.idx[cf.n] = tc.cf_tiles++; cf.sync[cf.n] = sync_after;
+  ++cf.n;
+  return (!tc.resident && sync_after >= 2) ? tile_fwd_flush(tc) : 0;
+}
+int tile_bwd_flush(TileChain& tc) {
+  TileChainBwdArgs& cb = tc.cb;
+  if (cb.n == 0) return 0;
+  int r;
+  if (cb.n == 1 && cb.kind[0] == TCS_TILE) {
+    r = tile_backward(tc.s, cb.b[0]);
+  } else if (cb.n == 1 && cb.kind[0] == TCS_STATS) {
+    r = tile_backward_stats(tc.s, cb.stats_dh, cb.stats_bn, cb.stats_rows, cb.stats_N);
+  } else if (cb.n == 1) {
+    const TileLatent& t = cb.lat;
+    r = gauss_latent_bwd(tc.s, t.mu_pre, t.ls_pre, t.eps, t.dz, t.kl_coeff, nullptr, t.dmu, t.dls,
+                         t.S, t.B, t.L);
+  } else {
+    cb.bar = tc.p->mid_bar; cb.bar_base = tc.p->mid_bar_count;
+    unsigned advance = 0;
+    r = tile_chain_backward(tc.s, cb, tc.tiles, &advance);
+    tc.p->mid_bar_count += advance;
+  }
+  cb.n = 0; tc.cb_tiles = 0;
+  return r;
+}
+int tile_bwd_stage(TileChain& tc, const TileBwdArgs& q, int sync_after) {
+  if (!tc.record) return tile_backward(tc.s, q);
+  TileChainBwdArgs& cb = tc.cb;
+  SCVAE_ARG(cb.n < TCR_MAX_STAGES && tc.cb_tiles < TCR_MAX_TILES);
+  cb.b[tc.cb_tiles] = q;
+  cb.kind[cb.n] = TCS_TILE; cb.idx[cb.n] = tc.cb_tiles++; cb.sync[cb.n] = sync_after;
+  ++cb.n;
+  return (!tc.resident && sync_after >= 2) ? tile_bwd_flush(tc) : 0;
+}
+// the fixed-order reduce of the pending dW / db slabs
+int tile_slab_flush(TileChain& tc) {
+  if (tc.pending.n_jobs == 0) return 0;
+  if (tc.cb.n != 0) TRY(tile_bwd_flush(tc));   // (a segment in flight still writes slabs of this table)
+  const int r = tile_slab_reduce(tc.s, tc.pending);
+  tc.pending.n_jobs = 0;
+  return r;
+}
+
+// the decoder going forward: one stage per layer -- normalise the layer below (the first reads
+// dec_in), the product, the chunk statistics of its output -- and a trailing stage that only
+// normalises the last layer: its h feeds the likelihood heads
+int tile_decoder_forward(TileChain& tc, std::vector<Dense>& dec, const float* dec_in, int L,
+                         int rows, int groups, int group_rows) {
+  scvae_plan* p = tc.p;
+  int cur = 0;
+  for (size_t i = 0; i <= dec.size(); ++i) {
+    TileFwdArgs q;
+    q.rows = rows;
+    if (i == 0) { q.x = dec_in; q.ldx = L; q.K = L; }
+    else {
+      q.K = dec[i - 1].n_out;
+      TRY(tile_bn_forward(p, tc.s, dec[i - 1], groups, group_rows, p->tc_part[cur],
+                          (rows + 63) / 64, 64, rows, &q.bn));
+    }
+    if (i < dec.size()) {
+      Dense& d = dec[i];
+      q.n_out = 1;
+      q.o[0].W = p->params + d.w; q.o[0].b = p->params + d.b; q.o[0].out = d.a;
+      q.o[0].part = p->tc_part[i == 0 ? cur : cur ^ 1]; q.o[0].N = d.n_out;
+    }
+    TRY(tile_fwd_stage(tc, q, 2));
+    if (i > 0) cur ^= 1;
+  }
+  return 0;
+}
+
+// one batch-normalised layer backwards: its own sums merged (per group), dA, d_in, its dW slab
+// (pending until tile_slab_flush) and the chunk sums of the layer `below`.  in == nullptr (the
+// layer that sees x): dA alone, written to dA_out -- its weight gradient is the count kernels' job
+int tile_layer_backward(TileChain& tc, Dense& d, Dense* below, const float* in, int rows,
+                        int groups, int group_rows, int64_t grows, const float* dh_in, float* d_in,
+                        float* dA_out) {
+  scvae_plan* p = tc.p;
+  SlabJobs& pending = tc.pending;
+  TileBwdArgs q;
+  const int G = (rows + 63) / 64;
+  q.rows = rows; q.inv_count = 1.f / (float)grows;
+  q.bessel = (float)grows / (float)(grows > 1 ? grows - 1 : 1);
+  q.n_up = 1;
+  if (in && pending.n_jobs == TC_MAX_JOBS) TRY(tile_slab_flush(tc));
+  float* slab = p->tc_slab[pending.n_jobs % TC_MAX_JOBS];
+  q.up[0].g = dh_in; q.up[0].W = p->params + d.w; q.up[0].N = d.n_out;
+  q.up[0].dW_slab = slab; q.up[0].dA_out = dA_out;
+  TRY(tile_bn_backward(p, tc.s, d, groups, group_rows, p->tc_spart[tc.sp], rows, q.bessel, &q.bn));
+  q.in = in; q.K = in ? d.n_in : 0; q.d_in = d_in;
+  if (below) q.below = tile_bn(p, *below, groups, group_rows, nullptr, 0, 0, p->tc_spart[tc.sp ^ 1]);
+  // what follows needs every tile's chunk sums (a layer below), every slab (the last stage)
+  // or -- the first decoder layer, then the latent stage -- the rows of this tile's cells
+  TRY(tile_bwd_stage(tc, q, (below || !in) ? 3 : (tc.S == 1 ? 1 : 3)));
+  if (!in) return 0;
+  pending.job[pending.n_jobs++] = {slab, p->grads + d.w, d.n_in * d.n_out, G};
+  tc.sp ^= 1;
+  return 0;
+}
+
+// the two posterior heads backwards: dW, db of both, dh of the layer `last` they sit on and --
+// where that layer belongs to the chain (chain_below) -- its chunk sums
+int tile_heads_backward(TileChain& tc, Dense& loc, Dense& scale, const float* dloc,
+                        const float* dscale, Dense& last, bool chain_below, int rows, int groups,
+                        int group_rows, int L, float* dh) {
+  scvae_plan* p = tc.p;
+  SlabJobs& pending = tc.pending;
+  const int G = (rows + 63) / 64, K = last.n_out;
+  if (pending.n_jobs + 4 > TC_MAX_JOBS) TRY(tile_slab_flush(tc));
+  float* slab2[2] = {p->tc_slab[pending.n_jobs], p->tc_slab[pending.n_jobs + 1]};
+  TileBwdArgs q;
+  q.rows = rows; q.n_up = 2;
+  for (int u = 0; u < 2; ++u) {
+    Dense& hd = u == 0 ? loc : scale;
+    q.up[u].g = u == 0 ? dloc : dscale;
+    q.up[u].W = p->params + hd.w; q.up[u].N = L;
+    q.up[u].dW_slab = slab2[u];
+    q.up[u].db_slab = slab2[u] + (size_t)G * 128 * 128;
+  }
+  q.in = last.h; q.K = K; q.d_in = dh;
+  if (chain_below)
+    q.below = tile_bn(p, last, groups, group_rows, nullptr, 0, 0, p->tc_spart[tc.sp]);
+  TRY(tile_bwd_stage(tc, q, 3));
+  // (jobs i and i + 1 own slab buffers i and i + 1; the two bias jobs ride in the same
+  //  buffers and only take job slots)
+  const int j0 = pending.n_jobs;
+  pending.job[j0] = {slab2[0], p->grads + loc.w, K * L, G};
+  pending.job[j0 + 1] = {slab2[1], p->grads + scale.w, K * L, G};
+  pending.job[j0 + 2] = {q.up[0].db_slab, p->grads + loc.b, L, G};
+  pending.job[j0 + 3] = {q.up[1].db_slab, p->grads + scale.b, L, G};
+  pending.n_jobs = j0 + 4;
   return 0;
 }
 
@@ -820,10 +985,9 @@ static int side_jobs(const scvae_side_work* w, hipStream_t st) {
   //  fits the infinity cache, it is as fast as before -- which is five launches' worth)
   const bool merge = w->fetch_out && w->fetch_n <= 512;
   if (w->noise_out && w->fetch_out && !merge) {
-    if ((rc = philox_normal(st, w->noise_out, w->noise_blocks * w->noise_block_rows,
-                            (int)w->noise_cols, w->noise_row_offset, w->noise_seed,
-                            w->noise_stream_id, w->noise_block_rows, w->noise_block_stride)))
-      return rc;
+    TRY(philox_normal(st, w->noise_out, w->noise_blocks * w->noise_block_rows,
+                      (int)w->noise_cols, w->noise_row_offset, w->noise_seed,
+                      w->noise_stream_id, w->noise_block_rows, w->noise_block_stride));
   } else if (w->noise_out) {
     nr.out = w->noise_out; nr.rows = w->noise_blocks * w->noise_block_rows;
     nr.cols = (int)w->noise_cols; nr.row_offset = w->noise_row_offset; nr.seed = w->noise_seed;
@@ -911,13 +1075,12 @@ int plan_side_fork(scvae_plan* p, hipStream_t s, int point) {
   SCVAE_HIP(hipEventRecord(p->side_fork, s));
   SCVAE_HIP(hipStreamWaitEvent(p->side_stream, p->side_fork, 0));
   p->side_forked = true;
-  int rc;
   if (jobs) {
-    if ((rc = side_jobs(w, p->side_stream))) return rc;
+    TRY(side_jobs(w, p->side_stream));
     p->side_jobs_done = true;
   }
   if (adam) {
-    if ((rc = side_adam(p, p->side_stream, p->heads_start, p->layout.n_params))) return rc;
+    TRY(side_adam(p, p->side_stream, p->heads_start, p->layout.n_params));
     p->side_adam_from = p->heads_start;
   }
   return 0;
@@ -940,239 +1103,26 @@ int plan_side_finish(scvae_plan* p, hipStream_t s) {
   return rc;
 }
 
-static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
+// ---- the head stage of a step: which likelihood path it takes (HeadPath, plan.hpp) ----
+// n_fwd: the separate forward passes of the step -- n_iw for the VAE (an importance-weighted
+// training step needs every log-likelihood before its weights), 1 for the GMVAE.  Decides the
+// path, raises what the step cannot do, and on the unfused path runs the heads' products.
+int head_path(scvae_plan* p, const scvae_step_args* a, hipStream_t s, bool training, int n_fwd,
+              const float* dch, int ld, int R, int B, HeadPath* out) {
   const scvae_model_config& c = p->cfg;
-  const int B = (int)a->cells;
-  const int S = a->deterministic_z ? 1 : a->n_iw * a->n_mc;
-  const int n_iw = a->deterministic_z ? 1 : a->n_iw;
-  const int n_mc = a->deterministic_z ? 1 : a->n_mc;
-  const int R = B * S;
-  const int F = c.feature_size, L = c.latent_size;
-  const bool training = a->training != 0;
-  const int64_t GB = a->global_cells > 0 ? a->global_cells : a->cells;
-  const float w = a->warm_up_weight * c.kl_weight;
-  int rc;
-  p->drop_seed = a->dropout_seed;
-
-  // ---------------- forward ----------------
-  if (training)
-    if ((rc = plan_side_fork(p, s, 0))) return rc;
-  const bool mid = mid_chain_ok(p, B, S, training);
-  const bool tile = !mid && tile_chain_ok(p, B, S, training);
-  // The tile stages of the pass: one launch each (default), or -- single process: a
-  // data-parallel hook needs the host between them -- RECORDED and launched together, both
-  // measured slower and off by default: in SEGMENTS (SCVAE_TILE_SEGMENTS=1: stages that only
-  // need their own tile's rows of the stage before -- posterior heads -> latent stage -> first
-  // decoder layer, one sample per cell -- in one launch behind a workgroup barrier,
-  // tile_chain_fwd_kernel; a stage that needs every tile's batch-norm statistics starts a new
-  // launch) or `resident` (scvae_plan_set_tile_resident: the whole pass in ONE launch, grid
-  // barriers where the segments end).
-  const bool resident = tile && tile_resident_ok(p, R);
-  const bool evalc = !mid && !tile && eval_chain_ok(p, a, B, S, training);
-  const bool record = resident || (tile && !p->sync && p->mid_bar && tile_segments_on());
-  TileChainFwdArgs cf;
-  int cf_tiles = 0;
-  auto fwd_flush = [&]() -> int {
-    if (cf.n == 0) return 0;
-    int r;
-    if (cf.n == 1 && cf.kind[0] == TCS_TILE) {
-      r = tile_forward(s, cf.f[0]);
-    } else if (cf.n == 1) {
-      const TileLatent& t = cf.lat;
-      r = gauss_latent_fwd(s, t.mu_pre, t.ls_pre, t.eps, t.z, t.kl_elem, t.kl_cell, nullptr, t.S,
-                           t.B, t.L, 0);
-    } else {
-      cf.bar = p->mid_bar; cf.bar_base = p->mid_bar_count;
-      unsigned advance = 0;
-      r = tile_chain_forward(s, cf, (R + 63) / 64, &advance);
-      p->mid_bar_count += advance;
-    }
-    cf.n = 0; cf_tiles = 0;
-    return r;
-  };
-  auto fwd_stage = [&](const TileFwdArgs& q, int sync_after) -> int {
-    if (!record) return tile_forward(s, q);
-    SCVAE_ARG(cf.n < TCR_MAX_STAGES && cf_tiles < TCR_MAX_TILES);
-    cf.f[cf_tiles] = q;
-    cf.kind[cf.n] = TCS_TILE; cf.idx[cf.n] = cf_tiles++; cf.sync[cf.n] = sync_after;
-    ++cf.n;
-    return (!resident && sync_after >= 2) ? fwd_flush() : 0;
-  };
-  const float* h = p->step_x;   // (the fp32 batch, or the token of the uint16 one: plan_gemm)
-  int ld = F;
-  if (mid) {
-    // the input-layer product, then everything up to the decoder's output in one workgroup
-    Dense& d0 = p->enc[0];
-    if ((rc = plan_gemm(p, s, false, false, p->step_x, p->params + d0.w, p->params + d0.b, d0.a, B,
-                        d0.n_out, d0.n_in, F, d0.n_out, d0.n_out, ACT_NONE, false)))
-      return rc;
-    const MidChainArgs q = mid_chain_args(p, a, B, S, training, 0.f);
-    if ((rc = vae_mid_forward(s, q))) return rc;
-    p->mid_bar_count += vae_mid_barrier_advance(q, false);
-    h = p->enc.back().h; ld = p->enc.back().n_out;
-  } else if (tile) {
-    // the input layer's product, its chunk statistics, then one launch per layer: the consumer
-    // of a layer merges its statistics and normalises its own rows of it
-    Dense& d0 = p->enc[0];
-    if ((rc = plan_gemm(p, s, false, false, p->step_x, p->params + d0.w, p->params + d0.b, d0.a, B,
-                        d0.n_out, d0.n_in, F, d0.n_out, d0.n_out, ACT_NONE, false)))
-      return rc;
-    int chunk = 0, chunks = 0;
-    if ((rc = bn_stats_partial(s, d0.a, d0.n_out, B, d0.n_out, p->tc_part[0], &chunk, &chunks)))
-      return rc;
-    int cur = 0;
-    for (size_t i = 1; i < p->enc.size(); ++i) {
-      Dense& d = p->enc[i];
-      TileFwdArgs q;
-      q.rows = B; q.K = d.n_in;
-      if ((rc = tile_bn_forward(p, s, p->enc[i - 1], p->tc_part[cur], chunks, chunk, B, &q.bn)))
-        return rc;
-      q.n_out = 1;
-      q.o[0].W = p->params + d.w; q.o[0].b = p->params + d.b; q.o[0].out = d.a;
-      q.o[0].part = p->tc_part[cur ^ 1]; q.o[0].N = d.n_out;
-      if ((rc = fwd_stage(q, 2))) return rc;
-      cur ^= 1; chunk = 64; chunks = (B + 63) / 64;
-    }
-    {   // the two posterior heads on the normalised output of the last encoder layer
-      Dense& last = p->enc.back();
-      TileFwdArgs q;
-      q.rows = B; q.K = last.n_out;
-      if ((rc = tile_bn_forward(p, s, last, p->tc_part[cur], chunks, chunk, B, &q.bn))) return rc;
-      q.n_out = 2;
-      q.o[0].W = p->params + p->mu.w; q.o[0].b = p->params + p->mu.b; q.o[0].out = p->mu_pre;
-      q.o[0].N = L;
-      q.o[1].W = p->params + p->ls.w; q.o[1].b = p->params + p->ls.b; q.o[1].out = p->ls_pre;
-      q.o[1].N = L;
-      if ((rc = fwd_stage(q, 1))) return rc;     // (the latent stage needs the tile's own rows)
-    }
-    h = p->enc.back().h; ld = p->enc.back().n_out;
-  } else if (evalc) {
-    // the input layer's product, then everything up to the decoder's output in one launch
-    Dense& d0 = p->enc[0];
-    if ((rc = plan_gemm(p, s, false, false, p->step_x, p->params + d0.w, p->params + d0.b, d0.a, B,
-                        d0.n_out, d0.n_in, F, d0.n_out, d0.n_out, ACT_NONE, false)))
-      return rc;
-    // (the fetch / noise of the next step leave the stream here, as in the launch chain)
-    if ((rc = plan_side_fork(p, s, 4))) return rc;
-    if ((rc = eval_chain(p, a, s, B))) return rc;
-    h = p->enc.back().h; ld = p->enc.back().n_out;
-  } else {
-  bool first = true;
-  for (auto& d : p->enc) {
-    if ((rc = dense_forward(p, s, d, h, ld, B, 1, true, training))) return rc;
-    h = d.h; ld = d.n_out;
-    // (evaluation steps: the fetch / noise of the next step leave the stream here)
-    if (first && !training)
-      if ((rc = plan_side_fork(p, s, 4))) return rc;
-    first = false;
-  }
-  }
-  Dense& mu = p->mu;
-  Dense& ls = p->ls;
-  // every parameter layer draws its own mask of the encoder output (va:2281-2289)
-  const float* h_mu = h;
-  const float* h_ls = h;
-  int ld_mu = ld, ld_ls = ld;
-  const bool mc_kl = (c.latent_mode & 1) != 0;      // va:2633-2640
-  const bool unit_var = (c.latent_mode & 2) != 0;   // du:323-337
-  const float* ls_pre = unit_var ? nullptr : p->ls_pre;
-  if (record) {
-    // (tile_chain_ok: analytic KL, a log_sigma head, training: the stage restates that case)
-    SCVAE_ARG(cf.n < TCR_MAX_STAGES && !mc_kl && !unit_var && !a->deterministic_z && a->eps);
-    TileLatent& t = cf.lat;
-    t.mu_pre = p->mu_pre; t.ls_pre = p->ls_pre; t.eps = a->eps; t.z = p->z;
-    t.kl_elem = p->kl_elem; t.kl_cell = p->kl_cell; t.S = S; t.B = B; t.L = L;
-    cf.kind[cf.n] = TCS_LATENT; cf.sync[cf.n] = S == 1 ? 1 : 3;   // (decoder tile = its own cells)
-    ++cf.n;
-    if (!resident && S != 1)
-      if ((rc = fwd_flush())) return rc;
-  } else if (tile) {
-    if ((rc = gauss_latent_fwd(s, p->mu_pre, ls_pre, a->eps, p->z, p->kl_elem, p->kl_cell,
-                               mc_kl ? p->kl_cell : nullptr, S, B, L, a->deterministic_z)))
-      return rc;
-  } else if (!mid && !evalc) {
-  if ((rc = dense_input(p, s, mu, h, ld, B, training, &h_mu, &ld_mu))) return rc;
-  if ((rc = plan_gemm(p, s, false, false, h_mu, p->params + mu.w, p->params + mu.b, p->mu_pre, B, L,
-                      mu.n_in, ld_mu, L, L, ACT_NONE, false)))
-    return rc;
-  if (!unit_var) {
-    if ((rc = dense_input(p, s, ls, h, ld, B, training, &h_ls, &ld_ls))) return rc;
-    if ((rc = plan_gemm(p, s, false, false, h_ls, p->params + ls.w, p->params + ls.b, p->ls_pre, B,
-                        L, ls.n_in, ld_ls, L, L, ACT_NONE, false)))
-      return rc;
-  }
-  if ((rc = gauss_latent_fwd(s, p->mu_pre, ls_pre, a->eps, p->z, p->kl_elem, p->kl_cell,
-                             mc_kl ? p->kl_cell : nullptr, S, B, L, a->deterministic_z)))
-    return rc;
-  }
-  // (recorded stages: the latent stage has not run yet -- these follow its launch)
-  auto latent_outputs = [&]() -> int {
-    if (a->kl_neurons)
-      if (int r = col_sum(s, p->kl_elem, L, B, L, a->kl_neurons, 1.f / (float)GB, 0, p->partial)) return r;
-    if (a->q_z_mean)
-      if (int r = copy(s, p->mu_pre, a->q_z_mean, (size_t)B * L)) return r;
-    return 0;
-  };
-  if (!record)
-    if ((rc = latent_outputs())) return rc;
-
-  const int E = c.decoder_extra;
-  const float* dec_in = p->z;   // decoder input: z, or [z | extra] (va:2407-2441)
-  if (E > 0) {
-    if ((rc = concat_extra(s, p->z, L, a->decoder_extra, E, (size_t)R, (size_t)B, p->zcat)))
-      return rc;
-    dec_in = p->zcat;
-  }
-  const float* dch = dec_in;
-  ld = L + E;
-  if (mid) {
-    dch = p->dec.back().h; ld = p->dec.back().n_out;
-  } else if (tile) {
-    int cur = 0;
-    for (size_t i = 0; i <= p->dec.size(); ++i) {
-      TileFwdArgs q;
-      q.rows = R;
-      if (i == 0) { q.x = dec_in; q.ldx = L; q.K = L; }
-      else {
-        q.K = p->dec[i - 1].n_out;
-        if ((rc = tile_bn_forward(p, s, p->dec[i - 1], p->tc_part[cur], (R + 63) / 64, 64, R,
-                                  &q.bn)))
-          return rc;
-      }
-      if (i < p->dec.size()) {
-        Dense& d = p->dec[i];
-        q.n_out = 1;
-        q.o[0].W = p->params + d.w; q.o[0].b = p->params + d.b; q.o[0].out = d.a;
-        q.o[0].part = p->tc_part[i == 0 ? cur : cur ^ 1]; q.o[0].N = d.n_out;
-      }   // (i == size: the last layer's normalisation alone -> its h feeds the likelihood heads)
-      if ((rc = fwd_stage(q, 2))) return rc;
-      if (i > 0) cur ^= 1;
-    }
-    if (record) {
-      if ((rc = fwd_flush())) return rc;
-      if ((rc = latent_outputs())) return rc;
-    }
-    dch = p->dec.back().h; ld = p->dec.back().n_out;
-  } else if (evalc) {
-    dch = p->dec.back().h; ld = p->dec.back().n_out;
-  } else {
-  for (auto& d : p->dec) {
-    if ((rc = dense_forward(p, s, d, dch, ld, R, 1, true, training))) return rc;
-    dch = d.h; ld = d.n_out;
-  }
-  }
-  HeadPtrs pre;
-  for (int j = 0; j < 3; ++j) pre.p[j] = p->pre[j];
-  const int h1 = p->heads[0].n_in;
+  HeadPath& hd = *out;
+  hd.training = training; hd.n_fwd = n_fwd; hd.dch = dch; hd.ld = ld; hd.R = R; hd.B = B;
+  for (int j = 0; j < 3; ++j) hd.pre.p[j] = p->pre[j];
+  const int h1 = hd.h1 = p->heads[0].n_in;
   // the fused kernel never materialises the [rows, P*F] pre-activations; the evaluate-time
   // statistics (p_x_mean, ...) need them, so that request takes the unfused path
-  const int KM = c.k_max;   // piecewise categorical likelihood: unfused path
+  const int KM = hd.KM = c.k_max;   // piecewise categorical likelihood: unfused path
   // dropout gives every head its own mask of the decoder output (va:2475-2488, 2507-2518): the
   // bf16x9 kernel has an instantiation that reads one dropped-out copy per head
   // (heads_fused_dropout_ok); otherwise that training pass is unfused
-  const bool head_drop = training && p->heads[0].keep > 0.f;
+  const bool head_drop = hd.head_drop = training && p->heads[0].keep > 0.f;
   // row softmax: three passes of the bf16x9 head kernel (decoder_fused_cpoisson), or unfused
-  const bool cpoisson = c.likelihood == LK_CPOISSON;
+  const bool cpoisson = hd.cpoisson = c.likelihood == LK_CPOISSON;
   if (cpoisson && !a->count_sum) {
     set_error("the constrained Poisson likelihood needs scvae_step_args.count_sum");
     return -1;
@@ -1183,142 +1133,468 @@ static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
   const bool fused_width =
       decoder_fused_supported(h1) ||
       (!head_drop && !cpoisson && decoder_fused_train_supported(p->P, h1, p->head_arith));
-  const bool fused = p->use_fused && p->fused_ws && fused_width && ld == h1 &&
-                     !a->p_x_mean && KM == 0 &&
-                     (!head_drop || (heads_fused_dropout_ok(p, n_iw) && !cpoisson)) &&
-                     (c.likelihood <= LK_ZINB || c.likelihood == LK_BERNOULLI ||
-                      (cpoisson && decoder_fused_cpoisson_supported(h1, p->head_arith)));
-  if (p->step_rows && (cpoisson || head_drop || (training && n_iw > 1))) {
+  hd.fused = p->use_fused && p->fused_ws && fused_width && ld == h1 && !a->p_x_mean && KM == 0 &&
+             (!head_drop || (heads_fused_dropout_ok(p, n_fwd) && !cpoisson)) &&
+             (c.likelihood <= LK_ZINB || c.likelihood == LK_BERNOULLI ||
+              (cpoisson && decoder_fused_cpoisson_supported(h1, p->head_arith)));
+  // (a GMVAE step never has a row index: scvae_plan_accepts_counts_rows)
+  if (p->step_rows && (cpoisson || head_drop || (training && n_fwd > 1))) {
     set_error("a row index needs a plain single-pass step (scvae_plan_accepts_counts_rows)");
     return -1;
   }
-  if (p->x_u16 && !fused) {
+  if (p->x_u16 && !hd.fused) {
     set_error("the uint16 minibatch needs the fused likelihood kernels (no -k / constrained "
               "Poisson, evaluation statistics, or head dropout outside the bf16x9 kernel)");
     return -1;
   }
-  const Targets tg = p->x_u16 ? targets_u16(p->step_u16, p->step_u16_ld) : targets_f32(a->t, F);
-  const HeadParams hp = head_params(p);
+  // (stacked passes read the same targets -- row r uses t[r % B]: as uint16 half the bytes)
+  hd.tg = p->x_u16 ? targets_u16(p->step_u16, p->step_u16_ld) : targets_f32(a->t, c.feature_size);
+  hd.hp = head_params(p);
   // -k (k = 1, 2) in a training step: two launches of the bf16x9 head kernel
   // (decoder_fused_train_cat) instead of materialised pre-activations and logits
-  const bool fused_cat = training && KM > 0 && p->use_fused && p->fused_ws &&
-                         p->pre_k && ld == h1 && !head_drop && !p->x_u16 && !a->p_x_mean &&
-                         decoder_fused_cat_supported(c.likelihood, KM, h1, p->head_arith);
+  hd.fused_cat = training && KM > 0 && p->use_fused && p->fused_ws && p->pre_k && ld == h1 &&
+                 !head_drop && !p->x_u16 && !a->p_x_mean &&
+                 decoder_fused_cat_supported(c.likelihood, KM, h1, p->head_arith);
   // ... and its forward half (two launches of decoder_forward_kernel) in evaluation passes and
   // in the first pass of an importance-weighted training step
-  const bool cat_forward = (!training || (fused_cat && n_iw > 1)) && KM > 0 && p->use_fused &&
-                           p->fused_ws && p->pre_k && ld == h1 && !p->x_u16 && !a->p_x_mean &&
-                           decoder_fused_forward_cat_supported(c.likelihood, KM, h1);
-  const float* head_in[4] = {dch, dch, dch, dch};   // [3]: the P_K head
-  if (!fused && !fused_cat && !cat_forward)
-    if ((rc = heads_forward(p, s, dch, ld, R, training, head_in))) return rc;
-  // per-row log-likelihood, forward only
-  auto loglik_forward = [&]() -> int {
-    if (fused && cpoisson)
-      return decoder_fused_cpoisson(s, false, dch, R, h1, hp, F, tg, B, nullptr, a->count_sum,
-                                    a->row_const, p->ll, nullptr, p->fused_ws);
-    if (fused)
-      return decoder_fused_forward(s, c.likelihood, dch, R, h1, hp, F, tg, B, a->row_const, p->ll,
-                                   p->fused_ws, p->head_arith, p->step_rows);
-    if (cat_forward)
-      return decoder_fused_forward_cat(s, c.likelihood, KM, dch, R, h1, hp,
-                                       p->params + p->head_k.w, p->params + p->head_k.b, F, a->t,
-                                       B, p->ll, p->fused_ws, p->pre_k);
-    if (KM > 0)
-      return loglik_cat_fwd(s, c.likelihood, a->t, F, pre, F, p->pre_k, KM, p->ll, R, B, F);
-    if (cpoisson)
-      return cpoisson_fwd(s, a->t, F, p->pre[0], F, a->count_sum, a->row_const, p->ll, R, B, F);
-    return loglik_fwd(s, c.likelihood, a->t, F, pre, F, a->row_const, p->ll, R, B, F);
-  };
+  hd.cat_forward = (!training || (hd.fused_cat && n_fwd > 1)) && KM > 0 && p->use_fused &&
+                   p->fused_ws && p->pre_k && ld == h1 && !p->x_u16 && !a->p_x_mean &&
+                   decoder_fused_forward_cat_supported(c.likelihood, KM, h1);
+  for (int j = 0; j < 4; ++j) hd.head_in[j] = dch;   // [3]: the P_K head
+  if (!hd.fused && !hd.fused_cat && !hd.cat_forward)
+    TRY(heads_forward(p, s, dch, ld, R, training, hd.head_in));
+  return 0;
+}
+// per-row log-likelihood, forward only
+int head_loglik_forward(scvae_plan* p, const scvae_step_args* a, hipStream_t s,
+                        const HeadPath& hd) {
+  const scvae_model_config& c = p->cfg;
+  const int F = c.feature_size, R = hd.R, B = hd.B, h1 = hd.h1, KM = hd.KM;
+  if (hd.fused && hd.cpoisson)
+    return decoder_fused_cpoisson(s, false, hd.dch, R, h1, hd.hp, F, hd.tg, B, nullptr,
+                                  a->count_sum, a->row_const, p->ll, nullptr, p->fused_ws);
+  if (hd.fused)
+    return decoder_fused_forward(s, c.likelihood, hd.dch, R, h1, hd.hp, F, hd.tg, B, a->row_const,
+                                 p->ll, p->fused_ws, p->head_arith, p->step_rows);
+  if (hd.cat_forward)
+    return decoder_fused_forward_cat(s, c.likelihood, KM, hd.dch, R, h1, hd.hp,
+                                     p->params + p->head_k.w, p->params + p->head_k.b, F, a->t, B,
+                                     p->ll, p->fused_ws, p->pre_k);
+  if (KM > 0)
+    return loglik_cat_fwd(s, c.likelihood, a->t, F, hd.pre, F, p->pre_k, KM, p->ll, R, B, F);
+  if (hd.cpoisson)
+    return cpoisson_fwd(s, a->t, F, p->pre[0], F, a->count_sum, a->row_const, p->ll, R, B, F);
+  return loglik_fwd(s, c.likelihood, a->t, F, hd.pre, F, a->row_const, p->ll, R, B, F);
+}
+// a step with p_x_mean: its argument checks; the constrained Poisson likelihood -- the statistics
+// want the rates, the likelihood the logits -- runs its likelihood first (*ll_done), then
+// normalises the logits in place
+int head_px_begin(scvae_plan* p, const scvae_step_args* a, hipStream_t s, const HeadPath& hd,
+                  bool* ll_done) {
+  if (!(a->p_x_stddev && a->stddev_of_p_x_given_z_mean)) {
+    set_error("p_x_mean requires p_x_stddev and stddev_of_p_x_given_z_mean");
+    return -1;
+  }
+  if (!hd.cpoisson) return 0;
+  if (hd.training) {
+    set_error("p_x_mean in a training step of the constrained Poisson likelihood");
+    return -1;
+  }
+  TRY(head_loglik_forward(p, a, s, hd));
+  *ll_done = true;
+  const int F = p->cfg.feature_size;
+  return cpoisson_rate(s, p->pre[0], F, a->count_sum, hd.R, hd.B, F);
+}
+// ... and, behind the caller's px_statistics, the two standard deviations
+int head_px_finish(scvae_plan* p, const scvae_step_args* a, hipStream_t s, const HeadPath& hd) {
+  const size_t n = (size_t)hd.B * p->cfg.feature_size;
+  TRY(sqrt_sum(s, p->vom, p->mov, a->p_x_stddev, n));
+  return sqrt_sum(s, p->vom, nullptr, a->stddev_of_p_x_given_z_mean, n);
+}
+// the likelihood launch of a training step: heads forward + likelihood + dW_j, db_j, dd in one
+// kernel (fused), two launches (-k), or the likelihood's backward on the materialised
+// pre-activations -- the heads' own backward then follows in head_backward
+int head_train(scvae_plan* p, const scvae_step_args* a, hipStream_t s, const HeadPath& hd,
+               float* dd) {
+  const scvae_model_config& c = p->cfg;
+  const int F = c.feature_size, R = hd.R, B = hd.B, h1 = hd.h1, KM = hd.KM;
+  if (hd.fused) {
+    HeadDropout hdrop;
+    if (hd.head_drop) TRY(heads_dropout_inputs(p, s, hd.dch, hd.ld, R, &hdrop));
+    if (hd.cpoisson)
+      return decoder_fused_cpoisson(s, true, hd.dch, R, h1, hd.hp, F, hd.tg, B, p->gw,
+                                    a->count_sum, a->row_const, p->ll, dd, p->fused_ws);
+    return decoder_fused_train(s, c.likelihood, hd.dch, R, h1, hd.hp, F, hd.tg, B, p->gw,
+                               a->row_const, p->ll, dd, p->fused_ws, p->head_arith, false,
+                               hd.head_drop ? &hdrop : nullptr, p->dd_atomics, p->step_rows);
+  }
+  if (hd.fused_cat) {
+    // (pre_k -- the logits' buffer of the unfused path -- is free: ll / dd of the second launch)
+    Dense& hk = p->head_k;
+    return decoder_fused_train_cat(s, c.likelihood, KM, hd.dch, R, h1, hd.hp, p->params + hk.w,
+                                   p->params + hk.b, p->grads + hk.w, p->grads + hk.b, F, a->t, B,
+                                   p->gw, p->ll, dd, p->fused_ws, p->head_arith, p->pre_k);
+  }
+  float* ll = hd.n_fwd == 1 ? p->ll : nullptr;   // (several passes: ll is the forward pass's)
+  if (KM > 0)
+    return loglik_cat_bwd(s, c.likelihood, a->t, F, hd.pre, F, p->pre_k, KM, p->gw, ll, R, B, F);
+  if (hd.cpoisson)
+    return cpoisson_bwd(s, a->t, F, p->pre[0], F, p->gw, a->count_sum, a->row_const, ll, R, B, F);
+  return loglik_bwd(s, c.likelihood, a->t, F, hd.pre, F, p->gw, a->row_const, ll, R, B, F);
+}
+int head_backward(scvae_plan* p, hipStream_t s, const HeadPath& hd, float* dd, float* scratch) {
+  if (hd.fused || hd.fused_cat) return 0;
+  return heads_backward(p, s, hd.head_in, hd.R, hd.head_drop, dd, scratch);
+}
+
+// ---- the VAE's step: what its stages share, and the stages of its four hidden-layer paths ----
+struct VaeStep {
+  scvae_plan* p; const scvae_step_args* a; hipStream_t s;
+  int B, S, n_iw, n_mc, R, F, L;
+  bool training, mc_kl, unit_var;
+  int64_t GB;
+  float w;
+  const float* ls_pre;
+  // launch chain: the (dropped-out) inputs of the two posterior heads, kept for their gradients
+  const float *h_mu = nullptr, *h_ls = nullptr;
+  int ld_mu = 0, ld_ls = 0;
+  const float* dec_in = nullptr;   // decoder input: z, or [z | extra] (va:2407-2441)
+  TileChain tc;
+};
+// the input layer's product x W1 + b (the chains start from it)
+static int vae_input_product(VaeStep& v) {
+  scvae_plan* p = v.p; hipStream_t s = v.s;
+  Dense& d0 = p->enc[0];
+  GEMM(false, false, p->step_x, p->params + d0.w, p->params + d0.b, d0.a, v.B, d0.n_out, d0.n_in,
+       v.F, d0.n_out, d0.n_out, ACT_NONE, false);
+  return 0;
+}
+// mid chain: everything up to the decoder's output in one workgroup
+static int vae_forward_mid(VaeStep& v) {
+  const MidChainArgs q = mid_chain_args(v.p, v.a, v.B, v.S, v.training, 0.f);
+  TRY(vae_mid_forward(v.s, q));
+  v.p->mid_bar_count += vae_mid_barrier_advance(q, false);
+  return 0;
+}
+// tile chain: the input layer's chunk statistics, then one stage per layer -- the consumer of a
+// layer merges its statistics and normalises its own rows of it --, the two posterior heads and
+// the latent stage
+static int vae_forward_tile(VaeStep& v) {
+  scvae_plan* p = v.p; hipStream_t s = v.s; const scvae_step_args* a = v.a;
+  const int B = v.B, S = v.S, L = v.L;
+  TileChain& tc = v.tc;
+  Dense& d0 = p->enc[0];
+  int chunk = 0, chunks = 0;
+  TRY(bn_stats_partial(s, d0.a, d0.n_out, B, d0.n_out, p->tc_part[0], &chunk, &chunks));
+  int cur = 0;
+  for (size_t i = 1; i < p->enc.size(); ++i) {
+    Dense& d = p->enc[i];
+    TileFwdArgs q;
+    q.rows = B; q.K = d.n_in;
+    TRY(tile_bn_forward(p, s, p->enc[i - 1], 1, 0, p->tc_part[cur], chunks, chunk, B, &q.bn));
+    q.n_out = 1;
+    q.o[0].W = p->params + d.w; q.o[0].b = p->params + d.b; q.o[0].out = d.a;
+    q.o[0].part = p->tc_part[cur ^ 1]; q.o[0].N = d.n_out;
+    TRY(tile_fwd_stage(tc, q, 2));
+    cur ^= 1; chunk = 64; chunks = (B + 63) / 64;
+  }
+  {   // the two posterior heads on the normalised output of the last encoder layer
+    Dense& last = p->enc.back();
+    TileFwdArgs q;
+    q.rows = B; q.K = last.n_out;
+    TRY(tile_bn_forward(p, s, last, 1, 0, p->tc_part[cur], chunks, chunk, B, &q.bn));
+    q.n_out = 2;
+    q.o[0].W = p->params + p->mu.w; q.o[0].b = p->params + p->mu.b; q.o[0].out = p->mu_pre;
+    q.o[0].N = L;
+    q.o[1].W = p->params + p->ls.w; q.o[1].b = p->params + p->ls.b; q.o[1].out = p->ls_pre;
+    q.o[1].N = L;
+    TRY(tile_fwd_stage(tc, q, 1));     // (the latent stage needs the tile's own rows)
+  }
+  if (!tc.record)
+    return gauss_latent_fwd(s, p->mu_pre, v.ls_pre, a->eps, p->z, p->kl_elem, p->kl_cell,
+                            v.mc_kl ? p->kl_cell : nullptr, S, B, L, a->deterministic_z);
+  // (tile_chain_ok: analytic KL, a log_sigma head, training: the stage restates that case)
+  TileChainFwdArgs& cf = tc.cf;
+  SCVAE_ARG(cf.n < TCR_MAX_STAGES && !v.mc_kl && !v.unit_var && !a->deterministic_z && a->eps);
+  TileLatent& t = cf.lat;
+  t.mu_pre = p->mu_pre; t.ls_pre = p->ls_pre; t.eps = a->eps; t.z = p->z;
+  t.kl_elem = p->kl_elem; t.kl_cell = p->kl_cell; t.S = S; t.B = B; t.L = L;
+  cf.kind[cf.n] = TCS_LATENT; cf.sync[cf.n] = S == 1 ? 1 : 3;   // (decoder tile = its own cells)
+  ++cf.n;
+  return (!tc.resident && S != 1) ? tile_fwd_flush(tc) : 0;
+}
+// evaluation chain: everything up to the decoder's output in one launch
+static int vae_forward_eval(VaeStep& v) {
+  // (the fetch / noise of the next step leave the stream here, as in the launch chain)
+  TRY(plan_side_fork(v.p, v.s, 4));
+  return eval_chain(v.p, v.a, v.s, v.B);
+}
+// launches: a chain of layers, the posterior heads (every parameter layer draws its own mask of
+// the encoder output, va:2281-2289) and the latent stage
+static int vae_forward_launches(VaeStep& v) {
+  scvae_plan* p = v.p; hipStream_t s = v.s; const scvae_step_args* a = v.a;
+  const int B = v.B, L = v.L;
+  const float* h = p->step_x;   // (the fp32 batch, or the token of the uint16 one: plan_gemm)
+  int ld = v.F;
+  bool first = true;
+  for (auto& d : p->enc) {
+    TRY(dense_forward(p, s, d, h, ld, B, 1, true, v.training));
+    h = d.h; ld = d.n_out;
+    // (evaluation steps: the fetch / noise of the next step leave the stream here)
+    if (first && !v.training) TRY(plan_side_fork(p, s, 4));
+    first = false;
+  }
+  Dense& mu = p->mu;
+  Dense& ls = p->ls;
+  v.h_mu = v.h_ls = h;
+  v.ld_mu = v.ld_ls = ld;
+  TRY(dense_input(p, s, mu, h, ld, B, v.training, &v.h_mu, &v.ld_mu));
+  GEMM(false, false, v.h_mu, p->params + mu.w, p->params + mu.b, p->mu_pre, B, L, mu.n_in, v.ld_mu,
+       L, L, ACT_NONE, false);
+  if (!v.unit_var) {
+    TRY(dense_input(p, s, ls, h, ld, B, v.training, &v.h_ls, &v.ld_ls));
+    GEMM(false, false, v.h_ls, p->params + ls.w, p->params + ls.b, p->ls_pre, B, L, ls.n_in,
+         v.ld_ls, L, L, ACT_NONE, false);
+  }
+  return gauss_latent_fwd(s, p->mu_pre, v.ls_pre, a->eps, p->z, p->kl_elem, p->kl_cell,
+                          v.mc_kl ? p->kl_cell : nullptr, v.S, B, L, a->deterministic_z);
+}
+// (recorded stages: these follow the launch that holds the latent stage)
+static int vae_latent_outputs(VaeStep& v) {
+  scvae_plan* p = v.p; const scvae_step_args* a = v.a;
+  if (a->kl_neurons)
+    TRY(col_sum(v.s, p->kl_elem, v.L, v.B, v.L, a->kl_neurons, 1.f / (float)v.GB, 0, p->partial));
+  if (a->q_z_mean) TRY(copy(v.s, p->mu_pre, a->q_z_mean, (size_t)v.B * v.L));
+  return 0;
+}
+
+// the input layer's weight gradient x^T dA (dA in dbuf[2]): what the chains leave for the end
+static int vae_input_gradient(VaeStep& v) {
+  scvae_plan* p = v.p; hipStream_t s = v.s;
+  Dense& d0 = p->enc[0];
+  TRY(plan_side_fork(p, s, 2));
+  return plan_gemm(p, s, true, false, p->step_x, p->dbuf[2], nullptr, p->grads + d0.w, d0.n_in,
+                   d0.n_out, v.B, v.F, d0.n_out, d0.n_out, ACT_NONE, false);
+}
+// mid chain: hidden layers, latent stage and posterior heads backwards in one workgroup
+static int vae_backward_mid(VaeStep& v) {
+  const MidChainArgs q = mid_chain_args(v.p, v.a, v.B, v.S, true, v.w / (float)v.GB);
+  TRY(vae_mid_backward(v.s, q));
+  v.p->mid_bar_count += vae_mid_barrier_advance(q, true);
+  return vae_input_gradient(v);
+}
+// tile chain: one stage per layer (+ the fixed-order reduce of the dW slabs): a layer's
+// batch-norm sums are merged by its own kernel, which also leaves the chunk sums of the layer below
+static int vae_backward_tile(VaeStep& v, float* dcur, float* dalt) {
+  scvae_plan* p = v.p; hipStream_t s = v.s; const scvae_step_args* a = v.a;
+  const int B = v.B, S = v.S, R = v.R, L = v.L;
+  const int64_t GB = v.GB, GR = GB * S;
+  TileChain& tc = v.tc;
+  TileChainBwdArgs& cb = tc.cb;   // (the recorded stages: launched in segments, as going forward)
+  {
+    Dense& top = p->dec.back();
+    const TileBN tb = tile_bn(p, top, 1, 0, nullptr, 0, 0, p->tc_spart[tc.sp]);
+    if (tc.record) {
+      cb.stats_dh = dcur; cb.stats_bn = tb; cb.stats_rows = R; cb.stats_N = top.n_out;
+      cb.kind[cb.n] = TCS_STATS; cb.sync[cb.n] = 3; ++cb.n;
+      if (!tc.resident) TRY(tile_bwd_flush(tc));
+    } else {
+      TRY(tile_backward_stats(s, dcur, tb, R, top.n_out));
+    }
+  }
+  for (int i = (int)p->dec.size() - 1; i >= 0; --i) {
+    const float* in = i > 0 ? p->dec[i - 1].h : v.dec_in;
+    TRY(tile_layer_backward(tc, p->dec[i], i > 0 ? &p->dec[i - 1] : nullptr, in, R, 1, 0, GR, dcur,
+                            i > 0 ? dalt : p->dz, nullptr));
+    if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
+  }
+  if (tc.record) {
+    SCVAE_ARG(cb.n < TCR_MAX_STAGES);
+    TileLatent& t = cb.lat;
+    t.mu_pre = p->mu_pre; t.ls_pre = p->ls_pre; t.eps = a->eps; t.dz = p->dz;
+    t.dmu = p->dmu; t.dls = p->dls; t.kl_coeff = v.w / (float)GB; t.S = S; t.B = B; t.L = L;
+    cb.kind[cb.n] = TCS_LATENT; cb.sync[cb.n] = 1; ++cb.n;   // (the heads' tile: the same cells)
+  } else {
+    TRY(gauss_latent_bwd(s, p->mu_pre, v.ls_pre, a->eps, p->dz, v.w / (float)GB, nullptr, p->dmu,
+                         p->dls, S, B, L));
+  }
+  float* dh = p->dbuf[0];
+  float* dh_alt = p->dbuf[1];
+  TRY(tile_heads_backward(tc, p->mu, p->ls, p->dmu, p->dls, p->enc.back(), true, B, 1, 0, L, dh));
+  for (int i = (int)p->enc.size() - 1; i >= 1; --i) {
+    TRY(tile_layer_backward(tc, p->enc[i], &p->enc[i - 1], p->enc[i - 1].h, B, 1, 0, GB, dh, dh_alt,
+                            nullptr));
+    float* t = dh; dh = dh_alt; dh_alt = t;
+  }
+  // the layer that sees x: its dA here, its weight gradient x^T dA on the count kernels
+  Dense& d0 = p->enc[0];
+  TRY(tile_layer_backward(tc, d0, nullptr, nullptr, B, 1, 0, GB, dh, nullptr, p->dbuf[2]));
+  // (the slab sums stay a launch of their own: every tile's slabs would have to cross the
+  //  XCDs' L2s behind a full release / acquire barrier)
+  if (tc.record) TRY(tile_bwd_flush(tc));
+  TRY(tile_slab_flush(tc));
+  if (p->sync && p->early_reduce_layer == &d0) {
+    // (data parallel: everything between ENCODER/1 and the likelihood heads is final -- its
+    //  all-reduce runs under x^T dA, as in dense_backward)
+    if (p->sync(p->sync_user, p->grads + p->early_reduce_start,
+                (int64_t)(p->heads_start - p->early_reduce_start), 2, 0)) {
+      set_error("gradient all-reduce hook failed");
+      return -2;
+    }
+  }
+  return vae_input_gradient(v);
+}
+// launches (and the evaluation chain's training counterpart): layer by layer
+static int vae_backward_launches(VaeStep& v, float* dcur, float* dalt) {
+  scvae_plan* p = v.p; hipStream_t s = v.s; const scvae_step_args* a = v.a;
+  const int B = v.B, S = v.S, R = v.R, L = v.L, E = p->cfg.decoder_extra;
+  const int64_t GB = v.GB, GR = GB * S;  // global decoder rows
+  float* scratch = p->dbuf[2];
+  // decoder layers, last to first; the first decoder layer's input is z
+  for (int i = (int)p->dec.size() - 1; i >= 0; --i) {
+    Dense& d = p->dec[i];
+    const float* in = i > 0 ? p->dec[i - 1].h : v.dec_in;
+    float* d_in = i > 0 ? dalt : (E > 0 ? p->dzcat : p->dz);
+    TRY(dense_backward(p, s, d, in, d.n_in, R, 1, true, dcur, scratch, d_in, false, GR));
+    if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
+  }
+  if (E > 0 && !p->dec.empty()) TRY(slice_cols(s, p->dzcat, L + E, L, (size_t)R, p->dz));
+  // no hidden layers: the heads sit directly on z, their dd is dz
+  if (p->dec.empty()) TRY(copy(s, dcur, p->dz, (size_t)R * L));
+  // latent: dz -> dmu_pre, dls_pre  (d(-ELBO_w)/dKL_cell = w / B_global)
+  //         Monte-Carlo KL: d(-ELBO_w)/dKL[s,b] = -w * gw[s,b]
+  TRY(gauss_latent_bwd(s, p->mu_pre, v.ls_pre, a->eps, p->dz, v.mc_kl ? v.w : v.w / (float)GB,
+                       v.mc_kl ? p->gw : nullptr, p->dmu, v.unit_var ? nullptr : p->dls, S, B, L));
+  float* dh = p->dbuf[0];
+  float* dh_alt = p->dbuf[1];
+  const bool need_dh = !p->enc.empty();
+  for (int q = 0; q < (v.unit_var ? 1 : 2); ++q) {
+    Dense& hd = q == 0 ? p->mu : p->ls;
+    const float* dpre = q == 0 ? p->dmu : p->dls;
+    const float* hq = q == 0 ? v.h_mu : v.h_ls;        // the (dropped-out) input of that layer
+    const int ldq = q == 0 ? v.ld_mu : v.ld_ls;
+    const bool drop = hd.keep > 0.f;
+    GEMM(true, false, hq, dpre, nullptr, p->grads + hd.w, hd.n_in, L, B, ldq, L, L, ACT_NONE, false);
+    TRY(col_sum(s, dpre, L, B, L, p->grads + hd.b, 1.f, 0, p->partial));
+    if (need_dh) {
+      TRY(gemm(s, false, true, dpre, p->params + hd.w, nullptr, drop ? dh_alt : dh, B, hd.n_in, L,
+               L, L, hd.n_in, ACT_NONE, !drop && q > 0, p->gemm_ws, p->gemm_ws_bytes));
+      if (drop) TRY(dense_input_backward(p, s, hd, dh_alt, dh, B, q > 0));
+    }
+  }
+  for (int i = (int)p->enc.size() - 1; i >= 0; --i) {
+    const float* in = i > 0 ? p->enc[i - 1].h : p->step_x;
+    TRY(dense_backward(p, s, p->enc[i], in, p->enc[i].n_in, B, 1, true, dh, scratch,
+                       i > 0 ? dh_alt : nullptr, false, GB));
+    if (i > 0) { float* t = dh; dh = dh_alt; dh_alt = t; }
+  }
+  // (the batch-norm moving averages were updated by the layers' backward statistics launches)
+  return 0;
+}
+
+static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
+  const scvae_model_config& c = p->cfg;
+  VaeStep v;
+  v.p = p; v.a = a; v.s = s;
+  const int B = v.B = (int)a->cells;
+  const int S = v.S = a->deterministic_z ? 1 : a->n_iw * a->n_mc;
+  const int n_iw = v.n_iw = a->deterministic_z ? 1 : a->n_iw;
+  const int n_mc = v.n_mc = a->deterministic_z ? 1 : a->n_mc;
+  const int R = v.R = B * S;
+  const int F = v.F = c.feature_size, L = v.L = c.latent_size;
+  const bool training = v.training = a->training != 0;
+  const int64_t GB = v.GB = a->global_cells > 0 ? a->global_cells : a->cells;
+  const float w = v.w = a->warm_up_weight * c.kl_weight;
+  const bool mc_kl = v.mc_kl = (c.latent_mode & 1) != 0;      // va:2633-2640
+  v.unit_var = (c.latent_mode & 2) != 0;                      // du:323-337
+  v.ls_pre = v.unit_var ? nullptr : p->ls_pre;
+  p->drop_seed = a->dropout_seed;
+
+  // ---------------- forward: hidden layers, posterior heads, latent stage ----------------
+  if (training) TRY(plan_side_fork(p, s, 0));
+  const bool mid = mid_chain_ok(p, B, S, training);
+  const bool tile = !mid && tile_chain_ok(p, B, S, training);
+  const bool evalc = !mid && !tile && eval_chain_ok(p, a, B, S, training);
+  // The tile stages of the pass: one launch each (default), or -- single process: a
+  // data-parallel hook needs the host between them -- RECORDED and launched together, both
+  // measured slower and off by default: in SEGMENTS (SCVAE_TILE_SEGMENTS=1: stages that only
+  // need their own tile's rows of the stage before -- posterior heads -> latent stage -> first
+  // decoder layer, one sample per cell -- in one launch behind a workgroup barrier,
+  // tile_chain_fwd_kernel; a stage that needs every tile's batch-norm statistics starts a new
+  // launch) or `resident` (scvae_plan_set_tile_resident: the whole pass in ONE launch, grid
+  // barriers where the segments end).
+  TileChain& tc = v.tc;
+  tc.p = p; tc.s = s; tc.S = S; tc.tiles = (R + 63) / 64;
+  tc.resident = tile && tile_resident_ok(p, R);
+  tc.record = tc.resident || (tile && !p->sync && p->mid_bar && tile_segments_on());
+  if (mid || tile || evalc) TRY(vae_input_product(v));
+  if (mid) TRY(vae_forward_mid(v));
+  else if (tile) TRY(vae_forward_tile(v));
+  else if (evalc) TRY(vae_forward_eval(v));
+  else TRY(vae_forward_launches(v));
+  if (!tc.record) TRY(vae_latent_outputs(v));
+
+  // ---------------- decoder ----------------
+  const int E = c.decoder_extra;
+  v.dec_in = p->z;
+  if (E > 0) {
+    TRY(concat_extra(s, p->z, L, a->decoder_extra, E, (size_t)R, (size_t)B, p->zcat));
+    v.dec_in = p->zcat;
+  }
+  const float* dch = v.dec_in;
+  int ld = L + E;
+  if (tile) {
+    TRY(tile_decoder_forward(tc, p->dec, v.dec_in, L, R, 1, 0));
+    if (tc.record) {
+      TRY(tile_fwd_flush(tc));
+      TRY(vae_latent_outputs(v));
+    }
+  } else if (!mid && !evalc) {
+    for (auto& d : p->dec) {
+      TRY(dense_forward(p, s, d, dch, ld, R, 1, true, training));
+      dch = d.h; ld = d.n_out;
+    }
+  }
+  if (mid || tile || evalc) { dch = p->dec.back().h; ld = p->dec.back().n_out; }
+
+  // ---------------- head stage, ELBO ----------------
+  HeadPath hd;
+  TRY(head_path(p, a, s, training, n_iw, dch, ld, R, B, &hd));
   bool ll_done = false;
   if (a->p_x_mean) {
-    if (!(a->p_x_stddev && a->stddev_of_p_x_given_z_mean)) {
-      set_error("p_x_mean requires p_x_stddev and stddev_of_p_x_given_z_mean");
-      return -1;
-    }
-    if (cpoisson) {
-      // the statistics want the rates, the likelihood the logits: likelihood first, then the
-      // logits are normalised in place
-      if (training) {
-        set_error("p_x_mean in a training step of the constrained Poisson likelihood");
-        return -1;
-      }
-      if ((rc = loglik_forward())) return rc;
-      ll_done = true;
-      if ((rc = cpoisson_rate(s, p->pre[0], F, a->count_sum, R, B, F))) return rc;
-    }
-    if (KM > 0)
-      rc = px_statistics_cat(s, c.likelihood, pre, F, p->pre_k, KM, S, B, F, nullptr, 0, 0,
-                             a->p_x_mean, p->mov, p->vom);
+    TRY(head_px_begin(p, a, s, hd, &ll_done));
+    if (hd.KM > 0)
+      TRY(px_statistics_cat(s, c.likelihood, hd.pre, F, p->pre_k, hd.KM, S, B, F, nullptr, 0, 0,
+                            a->p_x_mean, p->mov, p->vom));
     else
-      rc = px_statistics(s, c.likelihood, pre, F, S, B, F, nullptr, 0, 0, a->p_x_mean, p->mov,
-                         p->vom);
-    if (rc) return rc;
-    if ((rc = sqrt_sum(s, p->vom, p->mov, a->p_x_stddev, (size_t)B * F))) return rc;
-    if ((rc = sqrt_sum(s, p->vom, nullptr, a->stddev_of_p_x_given_z_mean, (size_t)B * F)))
-      return rc;
+      TRY(px_statistics(s, c.likelihood, hd.pre, F, S, B, F, nullptr, 0, 0, a->p_x_mean, p->mov,
+                        p->vom));
+    TRY(head_px_finish(p, a, s, hd));
   }
   const float row_scale = 1.f / ((float)n_mc * (float)GB);
   if (!training) {
-    if (!ll_done)
-      if ((rc = loglik_forward())) return rc;
-    if ((rc = vae_elbo(s, p->ll, p->kl_cell, mc_kl, n_iw, n_mc, B, w, row_scale, a->scalars, nullptr)))
-      return rc;
-    if (a->log_p_x_given_z)
-      if ((rc = copy(s, p->ll, a->log_p_x_given_z, (size_t)R))) return rc;
+    if (!ll_done) TRY(head_loglik_forward(p, a, s, hd));
+    TRY(vae_elbo(s, p->ll, p->kl_cell, mc_kl, n_iw, n_mc, B, w, row_scale, a->scalars, nullptr));
+    if (a->log_p_x_given_z) TRY(copy(s, p->ll, a->log_p_x_given_z, (size_t)R));
     return 0;
   }
-
-  // ---------------- backward ----------------
   float* dcur = p->dbuf[0];
   float* dalt = p->dbuf[1];
   if (n_iw == 1) {
     // d(-ELBO_w)/d log p = -1/(MC*B) for every row: known before the likelihood pass
     if (p->gw_rows < (size_t)R || p->gw_value != -row_scale) {
-      if ((rc = fill(s, p->gw, -row_scale, (size_t)R))) return rc;
+      TRY(fill(s, p->gw, -row_scale, (size_t)R));
       p->gw_value = -row_scale;
       p->gw_rows = (size_t)R;
     }
   } else {
     p->gw_rows = 0;   // vae_elbo below overwrites gw with the importance weights
     // importance weights need all log-likelihoods first
-    if ((rc = loglik_forward())) return rc;
-    if ((rc = vae_elbo(s, p->ll, p->kl_cell, mc_kl, n_iw, n_mc, B, w, row_scale, a->scalars, p->gw)))
-      return rc;
+    TRY(head_loglik_forward(p, a, s, hd));
+    TRY(vae_elbo(s, p->ll, p->kl_cell, mc_kl, n_iw, n_mc, B, w, row_scale, a->scalars, p->gw));
   }
-  if (fused) {
-    // heads forward + likelihood + dW_j, db_j, dd in one kernel
-    HeadDropout hdrop;
-    if (head_drop)
-      if ((rc = heads_dropout_inputs(p, s, dch, ld, R, &hdrop))) return rc;
-    if (cpoisson)
-      rc = decoder_fused_cpoisson(s, true, dch, R, h1, hp, F, tg, B, p->gw, a->count_sum,
-                                  a->row_const, p->ll, dcur, p->fused_ws);
-    else
-      rc = decoder_fused_train(s, c.likelihood, dch, R, h1, hp, F, tg, B, p->gw, a->row_const,
-                               p->ll, dcur, p->fused_ws, p->head_arith, false,
-                               head_drop ? &hdrop : nullptr, p->dd_atomics, p->step_rows);
-    if (rc) return rc;
-  } else if (fused_cat) {
-    // (pre_k -- the logits' buffer of the unfused path -- is free: ll / dd of the second launch)
-    Dense& hk = p->head_k;
-    if ((rc = decoder_fused_train_cat(s, c.likelihood, KM, dch, R, h1, hp, p->params + hk.w,
-                                      p->params + hk.b, p->grads + hk.w, p->grads + hk.b, F, a->t,
-                                      B, p->gw, p->ll, dcur, p->fused_ws, p->head_arith, p->pre_k)))
-      return rc;
-  } else {
-    if (KM > 0)
-      rc = loglik_cat_bwd(s, c.likelihood, a->t, F, pre, F, p->pre_k, KM, p->gw,
-                          n_iw == 1 ? p->ll : nullptr, R, B, F);
-    else if (cpoisson)
-      rc = cpoisson_bwd(s, a->t, F, p->pre[0], F, p->gw, a->count_sum, a->row_const,
-                        n_iw == 1 ? p->ll : nullptr, R, B, F);
-    else
-      rc = loglik_bwd(s, c.likelihood, a->t, F, pre, F, p->gw, a->row_const,
-                      n_iw == 1 ? p->ll : nullptr, R, B, F);
-    if (rc) return rc;
-    if ((rc = heads_backward(p, s, head_in, R, head_drop, dcur, dalt))) return rc;
-  }
+  TRY(head_train(p, a, s, hd, dcur));
+  TRY(head_backward(p, s, hd, dcur, dalt));
   if (p->sync && p->early_reduce_layer != nullptr) {
     // data parallel: the gradients of the likelihood heads -- two thirds of the buffer -- are
     // final; their all-reduce may run under the whole backward pass of the hidden layers
@@ -1328,238 +1604,15 @@ static int vae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
       return -2;
     }
   }
-  if ((rc = plan_side_fork(p, s, 1))) return rc;   // (scvae_step_args.side)
+  TRY(plan_side_fork(p, s, 1));   // (scvae_step_args.side)
   if (n_iw == 1)
-    if ((rc = vae_elbo(s, p->ll, p->kl_cell, mc_kl, n_iw, n_mc, B, w, row_scale, a->scalars, nullptr)))
-      return rc;
-  if (a->log_p_x_given_z)
-    if ((rc = copy(s, p->ll, a->log_p_x_given_z, (size_t)R))) return rc;
+    TRY(vae_elbo(s, p->ll, p->kl_cell, mc_kl, n_iw, n_mc, B, w, row_scale, a->scalars, nullptr));
+  if (a->log_p_x_given_z) TRY(copy(s, p->ll, a->log_p_x_given_z, (size_t)R));
 
-  if (mid) {
-    // hidden layers, latent stage and posterior heads backwards in one workgroup; what is left
-    // is the input layer's weight gradient x^T dA
-    const MidChainArgs q = mid_chain_args(p, a, B, S, true, w / (float)GB);
-    if ((rc = vae_mid_backward(s, q))) return rc;
-    p->mid_bar_count += vae_mid_barrier_advance(q, true);
-    Dense& d0 = p->enc[0];
-    if ((rc = plan_side_fork(p, s, 2))) return rc;
-    return plan_gemm(p, s, true, false, p->step_x, p->dbuf[2], nullptr, p->grads + d0.w, d0.n_in,
-                     d0.n_out, B, F, d0.n_out, d0.n_out, ACT_NONE, false);
-  }
-  const int64_t GR = GB * S;  // global decoder rows
-  if (tile) {
-    // one launch per layer (+ the fixed-order reduce of its dW slabs): the layer's batch-norm
-    // sums are merged by its own kernel, which also leaves the chunk sums of the layer below
-    auto bessel = [](int64_t n) { return (float)n / (float)(n > 1 ? n - 1 : 1); };
-    int sp = 0;
-    // the dW / db slabs of the layers wait for ONE fixed-order reduce at the end of the pass (they
-    // are not on the chain's critical path: four launches fewer); slab buffer i <-> pending job i
-    SlabJobs pending;
-    TileChainBwdArgs cb;          // (the recorded stages: launched in segments, as going forward)
-    int cb_tiles = 0;
-    auto bwd_flush = [&]() -> int {
-      if (cb.n == 0) return 0;
-      int r;
-      if (cb.n == 1 && cb.kind[0] == TCS_TILE) {
-        r = tile_backward(s, cb.b[0]);
-      } else if (cb.n == 1 && cb.kind[0] == TCS_STATS) {
-        r = tile_backward_stats(s, cb.stats_dh, cb.stats_bn, cb.stats_rows, cb.stats_N);
-      } else if (cb.n == 1) {
-        const TileLatent& t = cb.lat;
-        r = gauss_latent_bwd(s, t.mu_pre, t.ls_pre, t.eps, t.dz, t.kl_coeff, nullptr, t.dmu, t.dls,
-                             t.S, t.B, t.L);
-      } else {
-        cb.bar = p->mid_bar; cb.bar_base = p->mid_bar_count;
-        unsigned advance = 0;
-        r = tile_chain_backward(s, cb, (R + 63) / 64, &advance);
-        p->mid_bar_count += advance;
-      }
-      cb.n = 0; cb_tiles = 0;
-      return r;
-    };
-    auto bwd_stage = [&](const TileBwdArgs& q, int sync_after) -> int {
-      if (!record) return tile_backward(s, q);
-      SCVAE_ARG(cb.n < TCR_MAX_STAGES && cb_tiles < TCR_MAX_TILES);
-      cb.b[cb_tiles] = q;
-      cb.kind[cb.n] = TCS_TILE; cb.idx[cb.n] = cb_tiles++; cb.sync[cb.n] = sync_after;
-      ++cb.n;
-      return (!resident && sync_after >= 2) ? bwd_flush() : 0;
-    };
-    auto flush = [&]() -> int {
-      if (pending.n_jobs == 0) return 0;
-      if (cb.n != 0) {            // (a segment in flight still writes slabs of this table)
-        const int rf = bwd_flush();
-        if (rf) return rf;
-      }
-      const int r = tile_slab_reduce(s, pending);
-      pending.n_jobs = 0;
-      return r;
-    };
-    {
-      Dense& top = p->dec.back();
-      const TileBN tb = tile_bn(p, top, nullptr, 0, 0, p->tc_spart[sp]);
-      if (record) {
-        cb.stats_dh = dcur; cb.stats_bn = tb; cb.stats_rows = R; cb.stats_N = top.n_out;
-        cb.kind[cb.n] = TCS_STATS; cb.sync[cb.n] = 3; ++cb.n;
-        if (!resident)
-          if ((rc = bwd_flush())) return rc;
-      } else if ((rc = tile_backward_stats(s, dcur, tb, R, top.n_out))) {
-        return rc;
-      }
-    }
-    auto layer_backward = [&](Dense& d, Dense* below, const float* in, int rows, int64_t grows,
-                              const float* dh_in, float* d_in, float* dA_out) -> int {
-      TileBwdArgs q;
-      const int G = (rows + 63) / 64;
-      q.rows = rows; q.inv_count = 1.f / (float)grows; q.bessel = bessel(grows);
-      q.n_up = 1;
-      if (in && pending.n_jobs == TC_MAX_JOBS) { const int r = flush(); if (r) return r; }
-      float* slab = p->tc_slab[pending.n_jobs % TC_MAX_JOBS];
-      q.up[0].g = dh_in; q.up[0].W = p->params + d.w; q.up[0].N = d.n_out;
-      q.up[0].dW_slab = slab; q.up[0].dA_out = dA_out;
-      {
-        const int r = tile_bn_backward(p, s, d, p->tc_spart[sp], G, rows, q.bessel, &q.bn);
-        if (r) return r;
-      }
-      q.in = in; q.K = in ? d.n_in : 0; q.d_in = d_in;
-      if (below) q.below = tile_bn(p, *below, nullptr, 0, 0, p->tc_spart[sp ^ 1]);
-      // what follows needs every tile's chunk sums (a layer below), every slab (the last stage)
-      // or -- the first decoder layer, then the latent stage -- the rows of this tile's cells
-      int r = bwd_stage(q, (below || !in) ? 3 : (S == 1 ? 1 : 3));
-      if (r || !in) return r;
-      pending.job[pending.n_jobs++] = {slab, p->grads + d.w, d.n_in * d.n_out, G};
-      sp ^= 1;
-      return 0;
-    };
-    for (int i = (int)p->dec.size() - 1; i >= 0; --i) {
-      Dense& d = p->dec[i];
-      const float* in = i > 0 ? p->dec[i - 1].h : dec_in;
-      float* d_in = i > 0 ? dalt : p->dz;
-      if ((rc = layer_backward(d, i > 0 ? &p->dec[i - 1] : nullptr, in, R, GR, dcur, d_in, nullptr)))
-        return rc;
-      if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
-    }
-    if (record) {
-      SCVAE_ARG(cb.n < TCR_MAX_STAGES);
-      TileLatent& t = cb.lat;
-      t.mu_pre = p->mu_pre; t.ls_pre = p->ls_pre; t.eps = a->eps; t.dz = p->dz;
-      t.dmu = p->dmu; t.dls = p->dls; t.kl_coeff = w / (float)GB; t.S = S; t.B = B; t.L = L;
-      cb.kind[cb.n] = TCS_LATENT; cb.sync[cb.n] = 1; ++cb.n;   // (the heads' tile: the same cells)
-    } else if ((rc = gauss_latent_bwd(s, p->mu_pre, ls_pre, a->eps, p->dz, w / (float)GB, nullptr,
-                                      p->dmu, p->dls, S, B, L))) {
-      return rc;
-    }
-    float* dh = p->dbuf[0];
-    float* dh_alt = p->dbuf[1];
-    {   // the two posterior heads: dW, db of both, dh of the last encoder layer and its chunk sums
-      Dense& last = p->enc.back();
-      const int G = (B + 63) / 64, K = last.n_out;
-      if (pending.n_jobs + 4 > TC_MAX_JOBS) { if ((rc = flush())) return rc; }
-      float* slab2[2] = {p->tc_slab[pending.n_jobs], p->tc_slab[pending.n_jobs + 1]};
-      TileBwdArgs q;
-      q.rows = B; q.n_up = 2;
-      for (int u = 0; u < 2; ++u) {
-        Dense& hd = u == 0 ? p->mu : p->ls;
-        q.up[u].g = u == 0 ? p->dmu : p->dls;
-        q.up[u].W = p->params + hd.w; q.up[u].N = L;
-        q.up[u].dW_slab = slab2[u];
-        q.up[u].db_slab = slab2[u] + (size_t)G * 128 * 128;
-      }
-      q.in = last.h; q.K = K; q.d_in = dh;
-      q.below = tile_bn(p, last, nullptr, 0, 0, p->tc_spart[sp]);
-      if ((rc = bwd_stage(q, 3))) return rc;
-      // (jobs i and i + 1 own slab buffers i and i + 1; the two bias jobs ride in the same
-      //  buffers and only take job slots)
-      const int j0 = pending.n_jobs;
-      pending.job[j0] = {slab2[0], p->grads + p->mu.w, K * L, G};
-      pending.job[j0 + 1] = {slab2[1], p->grads + p->ls.w, K * L, G};
-      pending.job[j0 + 2] = {q.up[0].db_slab, p->grads + p->mu.b, L, G};
-      pending.job[j0 + 3] = {q.up[1].db_slab, p->grads + p->ls.b, L, G};
-      pending.n_jobs = j0 + 4;
-    }
-    for (int i = (int)p->enc.size() - 1; i >= 1; --i) {
-      if ((rc = layer_backward(p->enc[i], &p->enc[i - 1], p->enc[i - 1].h, B, GB, dh, dh_alt,
-                               nullptr)))
-        return rc;
-      float* t = dh; dh = dh_alt; dh_alt = t;
-    }
-    // the layer that sees x: its dA here, its weight gradient x^T dA on the count kernels
-    Dense& d0 = p->enc[0];
-    if ((rc = layer_backward(d0, nullptr, nullptr, B, GB, dh, nullptr, p->dbuf[2]))) return rc;
-    // (the slab sums stay a launch of their own: every tile's slabs would have to cross the
-    //  XCDs' L2s behind a full release / acquire barrier)
-    if (record)
-      if ((rc = bwd_flush())) return rc;
-    if ((rc = flush())) return rc;
-    if (p->sync && p->early_reduce_layer == &d0) {
-      // (data parallel: everything between ENCODER/1 and the likelihood heads is final -- its
-      //  all-reduce runs under x^T dA, as in dense_backward)
-      if (p->sync(p->sync_user, p->grads + p->early_reduce_start,
-                  (int64_t)(p->heads_start - p->early_reduce_start), 2, 0)) {
-        set_error("gradient all-reduce hook failed");
-        return -2;
-      }
-    }
-    if ((rc = plan_side_fork(p, s, 2))) return rc;
-    return plan_gemm(p, s, true, false, p->step_x, p->dbuf[2], nullptr, p->grads + d0.w, d0.n_in,
-                     d0.n_out, B, F, d0.n_out, d0.n_out, ACT_NONE, false);
-  }
-  // decoder layers, last to first; the first decoder layer's input is z
-  for (int i = (int)p->dec.size() - 1; i >= 0; --i) {
-    Dense& d = p->dec[i];
-    const float* in = i > 0 ? p->dec[i - 1].h : dec_in;
-    const int ld_in = d.n_in;
-    float* d_in = i > 0 ? dalt : (E > 0 ? p->dzcat : p->dz);
-    float* scratch = p->dbuf[2];
-    if ((rc = dense_backward(p, s, d, in, ld_in, R, 1, true, dcur, scratch, d_in, false, GR)))
-      return rc;
-    if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
-  }
-  if (E > 0 && !p->dec.empty())
-    if ((rc = slice_cols(s, p->dzcat, L + E, L, (size_t)R, p->dz))) return rc;
-  // no hidden layers: the heads sit directly on z, their dd is dz
-  if (p->dec.empty())
-    if ((rc = copy(s, dcur, p->dz, (size_t)R * L))) return rc;
-  // latent: dz -> dmu_pre, dls_pre  (d(-ELBO_w)/dKL_cell = w / B_global)
-  //         Monte-Carlo KL: d(-ELBO_w)/dKL[s,b] = -w * gw[s,b]
-  if ((rc = gauss_latent_bwd(s, p->mu_pre, ls_pre, a->eps, p->dz, mc_kl ? w : w / (float)GB,
-                             mc_kl ? p->gw : nullptr, p->dmu, unit_var ? nullptr : p->dls, S, B,
-                             L)))
-    return rc;
-  float* dh = p->dbuf[0];
-  float* dh_alt = p->dbuf[1];
-  const bool need_dh = !p->enc.empty();
-  for (int q = 0; q < (unit_var ? 1 : 2); ++q) {
-    Dense& hd = q == 0 ? mu : ls;
-    const float* dpre = q == 0 ? p->dmu : p->dls;
-    const float* hq = q == 0 ? h_mu : h_ls;        // the (dropped-out) input of that layer
-    const int ldq = q == 0 ? ld_mu : ld_ls;
-    const bool drop = hd.keep > 0.f;
-    if ((rc = plan_gemm(p, s, true, false, hq, dpre, nullptr, p->grads + hd.w, hd.n_in, L, B, ldq,
-                        L, L, ACT_NONE, false)))
-      return rc;
-    if ((rc = col_sum(s, dpre, L, B, L, p->grads + hd.b, 1.f, 0, p->partial))) return rc;
-    if (need_dh) {
-      if ((rc = gemm(s, false, true, dpre, p->params + hd.w, nullptr, drop ? dh_alt : dh, B,
-                     hd.n_in, L, L, L, hd.n_in, ACT_NONE, !drop && q > 0, p->gemm_ws,
-                     p->gemm_ws_bytes)))
-        return rc;
-      if (drop)
-        if ((rc = dense_input_backward(p, s, hd, dh_alt, dh, B, q > 0))) return rc;
-    }
-  }
-  for (int i = (int)p->enc.size() - 1; i >= 0; --i) {
-    Dense& d = p->enc[i];
-    const float* in = i > 0 ? p->enc[i - 1].h : p->step_x;
-    const int ld_in = d.n_in;
-    float* d_in = i > 0 ? dh_alt : nullptr;
-    float* scratch = p->dbuf[2];
-    if ((rc = dense_backward(p, s, d, in, ld_in, B, 1, true, dh, scratch, d_in, false, GB)))
-      return rc;
-    if (i > 0) { float* t = dh; dh = dh_alt; dh_alt = t; }
-  }
-  // (the batch-norm moving averages were updated by the layers' backward statistics launches)
-  return 0;
+  // ---------------- backward of the chosen path ----------------
+  if (mid) return vae_backward_mid(v);
+  if (tile) return vae_backward_tile(v, dcur, dalt);
+  return vae_backward_launches(v, dcur, dalt);
 }
 
 }  // namespace scvae
@@ -1720,6 +1773,7 @@ int scvae_plan_set_dd_atomics(scvae_plan* p, int32_t enabled) {
   p->dd_atomics = enabled ? 1 : 0;
   return 0;
 }
+int32_t scvae_plan_dd_atomics(const scvae_plan* p) { return p ? p->dd_atomics : -1; }
 
 int scvae_plan_probe_heads(scvae_plan* p, int32_t n) {
   SCVAE_ARG(p && n >= 0 && n <= 4096);
@@ -1858,27 +1912,24 @@ int scvae_plan_decode(scvae_plan* p, const float* z, int64_t rows, float* p_x_me
   const scvae_model_config& c = p->cfg;
   const int R = (int)rows, F = c.feature_size;
   std::vector<Dense>& dec = c.model_type == SCVAE_MODEL_GMVAE ? p->xdec : p->dec;
-  int rc;
   const float* h = z;
   int ld = c.latent_size;
   for (auto& d : dec) {
-    if ((rc = dense_forward(p, s, d, h, ld, R, 1, true, false))) return rc;
+    TRY(dense_forward(p, s, d, h, ld, R, 1, true, false));
     h = d.h; ld = d.n_out;
   }
   HeadPtrs pre;
   for (int j = 0; j < 3; ++j) pre.p[j] = p->pre[j];
   for (int j = 0; j < p->P; ++j) {
     Dense& hd = p->heads[j];
-    if ((rc = gemm(s, false, false, h, p->params + hd.w, p->params + hd.b, p->pre[j], R, F, hd.n_in,
-                   ld, F, F, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
+    TRY(gemm(s, false, false, h, p->params + hd.w, p->params + hd.b, p->pre[j], R, F, hd.n_in,
+             ld, F, F, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes));
   }
   if (c.k_max > 0) {
     Dense& hk = p->head_k;
     const int FC = F * (c.k_max + 1);
-    if ((rc = gemm(s, false, false, h, p->params + hk.w, p->params + hk.b, p->pre_k, R, FC, hk.n_in,
-                   ld, FC, FC, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes)))
-      return rc;
+    TRY(gemm(s, false, false, h, p->params + hk.w, p->params + hk.b, p->pre_k, R, FC, hk.n_in,
+             ld, FC, FC, ACT_NONE, false, p->gemm_ws, p->gemm_ws_bytes));
     return px_statistics_cat(s, c.likelihood, pre, F, p->pre_k, c.k_max, 1, R, F, nullptr, 0, 0,
                              p_x_mean, p->mov, p->vom);
   }
@@ -2125,359 +2176,6 @@ int scvae_plan_step(scvae_plan* p, const scvae_step_args* a, void* stream) {
   }
   if (!rc && p->ws_guards_dev) rc = scvae::ws_guard_check(p, (hipStream_t)stream);
   return rc;
-}
-
-int scvae_adam_clip_step(float* theta, float* grad, float* m, float* v, int64_t n,
-                         float grad_scale, float lr_t, float beta1, float beta2, float epsilon,
-                         void* stream) {
-  SCVAE_ARG(n >= 0);
-  return scvae::adam_clip_step((hipStream_t)stream, theta, grad, m, v, (size_t)n, grad_scale, lr_t,
-                               beta1, beta2, epsilon);
-}
-
-int scvae_gemm(int32_t ta, int32_t tb, const float* A, const float* B, const float* bias, float* C,
-               int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t relu,
-               int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
-  return scvae::gemm((hipStream_t)stream, ta != 0, tb != 0, A, B, bias, C, (int)M, (int)N, (int)K,
-                     (int)lda, (int)ldb, (int)ldc, relu ? scvae::ACT_RELU : scvae::ACT_NONE,
-                     accumulate != 0, (float*)workspace, (size_t)workspace_bytes);
-}
-int scvae_count_gemm(int32_t mode, const float* x, int64_t ldx, int64_t rows, int64_t cols,
-                     const float* other, int64_t ld_other, int64_t N, const float* bias,
-                     int32_t relu, float* C, int64_t ldc, void* workspace, int64_t workspace_bytes,
-                     void* stream) {
-  SCVAE_ARG(workspace_bytes >= 0);
-  return scvae::count_gemm((hipStream_t)stream, mode, x, (int)ldx, (int)rows, (int)cols, other,
-                           (int)ld_other, (int)N, bias, relu ? scvae::ACT_RELU : scvae::ACT_NONE,
-                           C, (int)ldc, workspace, (size_t)workspace_bytes);
-}
-int64_t scvae_count_gemm_workspace_bytes(int32_t mode, int64_t rows, int64_t cols, int64_t N) {
-  if (!scvae::count_gemm_supported((int)N)) return -1;
-  return (int64_t)scvae::count_gemm_workspace_bytes(mode, (int)rows, (int)cols, (int)N);
-}
-int scvae_check_counts(const float* values, int64_t n, int32_t* bad, void* stream) {
-  SCVAE_ARG(n >= 0);
-  return scvae::check_counts((hipStream_t)stream, values, (size_t)n, bad);
-}
-int64_t scvae_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  return (int64_t)scvae::gemm_workspace_bytes((int)M, (int)N, (int)K);
-}
-
-int scvae_loglik_fwd(int32_t kind, const float* t, const float* const* pre, const float* row_const,
-                     float* ll, int64_t rows, int64_t cells, int64_t F, void* stream) {
-  SCVAE_ARG(pre && kind >= 0 && kind <= 3);
-  scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
-  for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = const_cast<float*>(pre[j]);
-  return scvae::loglik_fwd((hipStream_t)stream, kind, t, (int)F, hp, (int)F, row_const, ll,
-                           (int)rows, (int)cells, (int)F);
-}
-int scvae_loglik_bwd(int32_t kind, const float* t, float* const* pre, const float* gw,
-                     const float* row_const, float* ll, int64_t rows, int64_t cells, int64_t F,
-                     void* stream) {
-  SCVAE_ARG(pre && kind >= 0 && kind <= 3);
-  scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
-  for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = pre[j];
-  return scvae::loglik_bwd((hipStream_t)stream, kind, t, (int)F, hp, (int)F, gw, row_const, ll,
-                           (int)rows, (int)cells, (int)F);
-}
-int64_t scvae_decoder_fused_workspace_bytes(int64_t rows, int64_t H, int64_t F) {
-  if (!scvae::decoder_fused_train_supported(1, (int)H, 1)) return -1;
-  return (int64_t)(scvae::decoder_fused_workspace_floats((int)rows, (int)H, (int)F, true) *
-                   sizeof(float));
-}
-int32_t scvae_decoder_fused_variant(int32_t kind, int64_t H) {
-  if (kind < 0 || (kind > 3 && kind != scvae::LK_BERNOULLI) ||
-      !scvae::decoder_fused_supported((int)H))
-    return 0;
-  return scvae::decoder_fused_variant(scvae::likelihood_heads(kind), (int)H);
-}
-int32_t scvae_default_head_arith(void) { return scvae::default_head_arith(); }
-int32_t scvae_default_dd_atomics(void) { return scvae::default_dd_atomics(); }
-int32_t scvae_plan_dd_atomics(const scvae_plan* p) { return p ? p->dd_atomics : -1; }
-int scvae_decoder_train_kernel_name(int32_t kind, int64_t H, int64_t rows, int32_t arith,
-                                    int32_t u16, char* out, int64_t n) {
-  SCVAE_ARG(out && n > 0);
-  out[0] = 0;
-  const int which = scvae_decoder_train_kernel(kind, H, arith);
-  SCVAE_ARG(which > 0);
-  const int P = scvae::likelihood_heads(kind);
-  if (which == 3) {
-    scvae::decoder_fused3_train_kernel_name(kind, (int)H, (int)rows, u16 != 0, out, (size_t)n,
-                                            arith == 2 ? 6 : 9);
-  } else if (which == 2) {
-    snprintf(out, (size_t)n, "decoder_head2_kernel<%d, true, %s>", kind,
-             (P <= 2 && H > 96 && H <= 111) ? "true|false" : "false");
-  } else {
-    snprintf(out, (size_t)n, "decoder_head_kernel<%d, true, %d>", kind, P >= 3 ? 32 : 64);
-  }
-  return 0;
-}
-int32_t scvae_decoder_train_kernel(int32_t kind, int64_t H, int32_t arith) {
-  if (kind < 0 || (kind > 3 && kind != scvae::LK_BERNOULLI) || (arith < 0 || arith > 2) ||
-      !scvae::decoder_fused_train_supported(scvae::likelihood_heads(kind), (int)H, arith))
-    return 0;
-  return scvae::decoder_train_kernel(scvae::likelihood_heads(kind), (int)H, arith);
-}
-static int decoder_fused_entry(int32_t kind, int32_t train, const float* d, int64_t rows, int64_t H,
-                               const float* const* W, const float* const* b, float* const* dW,
-                               float* const* db, int64_t F, scvae::Targets t, int64_t cells,
-                               const float* gw, const float* row_const, float* ll, float* dd,
-                               void* workspace, void* stream) {
-  SCVAE_ARG(((kind >= 0 && kind <= 3) || kind == scvae::LK_BERNOULLI) && W && b);
-  // bits 8, 9, 11 of `train`: the arithmetic of this call (none: the process default)
-  const int arith_bits = train & (SCVAE_HEADS_FP32 | SCVAE_HEADS_BF16X9 | SCVAE_HEADS_BF16X6);
-  SCVAE_ARG((train & ~0xF03) == 0 && (arith_bits & (arith_bits - 1)) == 0);
-  const int dd_mode = (train & SCVAE_HEADS_DD_ATOMICS) ? 1 : 0;
-  const int arith = (train & SCVAE_HEADS_FP32) ? 0
-                    : (train & SCVAE_HEADS_BF16X9) ? 1
-                    : (train & SCVAE_HEADS_BF16X6) ? 2 : scvae::default_head_arith();
-  train &= 3;
-  // (even widths up to 126: every arithmetic; the bf16x9 kernel's wider range -- odd widths, up
-  //  to 256 -- for training and, its forward half, forward-only calls)
-  SCVAE_ARG(scvae::decoder_fused_train_supported(scvae::likelihood_heads(kind), (int)H, arith));
-  scvae::HeadParams hp;
-  for (int j = 0; j < 3; ++j) {
-    const bool on = j < scvae::likelihood_heads(kind);
-    hp.W[j] = on ? W[j] : nullptr;
-    hp.b[j] = on ? b[j] : nullptr;
-    hp.dW[j] = (on && dW) ? dW[j] : nullptr;
-    hp.db[j] = (on && db) ? db[j] : nullptr;
-  }
-  if (train) {
-    SCVAE_ARG(dW && db);
-    return scvae::decoder_fused_train((hipStream_t)stream, kind, d, (int)rows, (int)H, hp, (int)F,
-                                      t, (int)cells, gw, row_const, ll, dd, (float*)workspace,
-                                      arith, (train & 2) != 0, nullptr, dd_mode);
-  }
-  return scvae::decoder_fused_forward((hipStream_t)stream, kind, d, (int)rows, (int)H, hp, (int)F,
-                                      t, (int)cells, row_const, ll, (float*)workspace, arith);
-}
-int scvae_decoder_fused(int32_t kind, int32_t train, const float* d, int64_t rows, int64_t H,
-                        const float* const* W, const float* const* b, float* const* dW,
-                        float* const* db, int64_t F, const float* t, int64_t cells,
-                        const float* gw, const float* row_const, float* ll, float* dd,
-                        void* workspace, void* stream) {
-  return decoder_fused_entry(kind, train, d, rows, H, W, b, dW, db, F,
-                             scvae::targets_f32(t, (int)F), cells, gw, row_const, ll, dd,
-                             workspace, stream);
-}
-int scvae_decoder_fused_u16(int32_t kind, int32_t train, const float* d, int64_t rows, int64_t H,
-                            const float* const* W, const float* const* b, float* const* dW,
-                            float* const* db, int64_t F, const uint16_t* t, int64_t ldt,
-                            int64_t cells, const float* gw, const float* row_const, float* ll,
-                            float* dd, void* workspace, void* stream) {
-  SCVAE_ARG(t && ldt >= (F + 63) / 64 * 64 && (ldt & 7) == 0 && ((uintptr_t)t & 15) == 0);
-  return decoder_fused_entry(kind, train, d, rows, H, W, b, dW, db, F,
-                             scvae::targets_u16(t, (int)ldt), cells, gw, row_const, ll, dd,
-                             workspace, stream);
-}
-int scvae_likelihood_elementwise(int32_t kind, const float* t, const float* const* pre,
-                                 float* log_prob, float* mean, float* variance, int64_t n,
-                                 void* stream) {
-  SCVAE_ARG(pre && ((kind >= 0 && kind <= 3) || kind == LK_BERNOULLI) && n >= 0);
-  scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
-  for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = const_cast<float*>(pre[j]);
-  return scvae::loglik_elementwise((hipStream_t)stream, kind, t, hp, log_prob, mean, variance,
-                                   (size_t)n);
-}
-int scvae_gauss_latent_fwd(const float* mu_pre, const float* ls_pre, const float* eps, float* z,
-                           float* kl_elem, float* kl_cell, int64_t S, int64_t cells, int64_t L,
-                           int32_t deterministic, void* stream) {
-  return scvae::gauss_latent_fwd((hipStream_t)stream, mu_pre, ls_pre, eps, z, kl_elem, kl_cell,
-                                 nullptr, (int)S, (int)cells, (int)L, deterministic);
-}
-int scvae_dropout_apply(const float* in, float* out, int64_t rows, int64_t cols, float keep,
-                        uint64_t seed, int32_t site, int32_t accumulate, void* stream) {
-  SCVAE_ARG(site >= 0 && cols > 0 && cols <= INT32_MAX);
-  return scvae::dropout_apply((hipStream_t)stream, in, (int)cols, out, (int)cols, rows, (int)cols,
-                              keep, seed, (uint32_t)site, accumulate);
-}
-int scvae_csr_minibatch(const int64_t* indptr, const int32_t* indices, const float* values,
-                        const int64_t* rows, int64_t n, int64_t F, void* out, int64_t ld,
-                        int32_t as_u16, const float* row_values, float* row_values_out,
-                        void* stream) {
-  SCVAE_ARG(as_u16 == 0 || as_u16 == 1);
-  if (as_u16)
-    return scvae::csr_densify_u16((hipStream_t)stream, indptr, indices, values, rows, (int)n,
-                                  (int)F, static_cast<uint16_t*>(out), (int)ld, row_values,
-                                  row_values_out);
-  return scvae::csr_densify((hipStream_t)stream, indptr, indices, values, rows, (int)n, (int)F,
-                            static_cast<float*>(out), (int)ld, row_values, row_values_out);
-}
-
-int scvae_csr_densify_u16(const int64_t* indptr, const int32_t* indices, const float* values,
-                          const int64_t* rows, int64_t n, int64_t F, uint16_t* out, int64_t ld,
-                          void* stream) {
-  return scvae::csr_densify_u16((hipStream_t)stream, indptr, indices, values, rows, (int)n, (int)F,
-                                out, (int)ld);
-}
-
-int scvae_count_gemm_u16(int32_t mode, const uint16_t* x, int64_t ldx, int64_t rows, int64_t cols,
-                         const float* other, int64_t ld_other, int64_t N, const float* bias,
-                         int32_t relu, float* C, int64_t ldc, void* workspace,
-                         int64_t workspace_bytes, void* stream) {
-  SCVAE_ARG(workspace_bytes >= 0);
-  return scvae::count_gemm_u16((hipStream_t)stream, mode, x, (int)ldx, (int)rows, (int)cols, other,
-                               (int)ld_other, (int)N, bias,
-                               relu ? scvae::ACT_RELU : scvae::ACT_NONE, C, (int)ldc, workspace,
-                               (size_t)workspace_bytes);
-}
-
-int64_t scvae_count_tiles_padded(int64_t F) {
-  return scvae::count_tiles_supported((int)F) && F > 0 && F <= 65536 ? scvae::count_tiles_padded((int)F) : -1;
-}
-int scvae_csr_row_entries(const int64_t* indptr, const float* values, int64_t n_rows, int32_t* out,
-                          void* stream) {
-  return scvae::csr_row_entries((hipStream_t)stream, indptr, values, n_rows, out);
-}
-int scvae_csr_count_tiles(const int64_t* indptr, const int32_t* indices, const float* values,
-                          const int64_t* rows, int64_t n, int64_t F,
-                          const scvae_count_tiles* tiles, void* stream) {
-  SCVAE_ARG(tiles && n >= 0 && n <= INT32_MAX && F > 0 && F <= 65536);
-  return scvae::csr_count_tiles((hipStream_t)stream, indptr, indices, values, rows, (int)n, (int)F,
-                                scvae::count_tiles_of(tiles));
-}
-int scvae_count_gemm_tiles(int32_t mode, const scvae_count_tiles* tiles, const uint16_t* x,
-                           int64_t ldx, int64_t rows, int64_t cols, const float* other,
-                           int64_t ld_other, int64_t N, const float* bias, int32_t relu, float* C,
-                           int64_t ldc, void* workspace, int64_t workspace_bytes, void* stream) {
-  SCVAE_ARG(tiles && workspace_bytes >= 0);
-  return scvae::count_gemm_tiles((hipStream_t)stream, mode, scvae::count_tiles_of(tiles), x, (int)ldx,
-                                 (int)rows, (int)cols, other, (int)ld_other, (int)N, bias,
-                                 relu ? scvae::ACT_RELU : scvae::ACT_NONE, C, (int)ldc, workspace,
-                                 (size_t)workspace_bytes);
-}
-
-int scvae_csr_densify(const int64_t* indptr, const int32_t* indices, const float* values,
-                      const int64_t* rows, int64_t n, int64_t F, float* out, void* stream) {
-  return scvae::csr_densify((hipStream_t)stream, indptr, indices, values, rows, (int)n, (int)F, out,
-                            (int)F);
-}
-int scvae_csr_row_lgamma1p(const int64_t* indptr, const float* values, int64_t n_rows, float* out,
-                           void* stream) {
-  return scvae::csr_row_lgamma1p((hipStream_t)stream, indptr, values, n_rows, out);
-}
-int scvae_gather_rows(const float* src, const int64_t* rows, int64_t n, float* out, void* stream) {
-  return scvae::gather_rows_f32((hipStream_t)stream, src, rows, (int)n, out);
-}
-int scvae_bn_merge(const float* gathered, const int64_t* counts, int64_t ranks, int64_t n,
-                   float* out, void* stream) {
-  return scvae::bn_merge((hipStream_t)stream, gathered, counts, (int)ranks, (int)n, out);
-}
-int64_t scvae_bn_workspace_floats(int64_t N) {
-  return N > 0 ? (int64_t)scvae::bn_partial_floats(1, (int)N) : -1;
-}
-int scvae_bn_stats(const float* a, int64_t lda, int64_t rows, int64_t N, float* mean, float* var,
-                   float* workspace, void* stream) {
-  SCVAE_ARG(rows > 0 && rows <= INT32_MAX && N > 0 && lda >= N);
-  return scvae::bn_stats((hipStream_t)stream, a, (int)lda, (int)rows, 1, (int)N, mean, var,
-                         workspace);
-}
-int scvae_bn_apply_relu_fwd(const float* a, int64_t lda, const float* mean, const float* var,
-                            const float* beta, float* h, int64_t ldh, int64_t rows, int64_t N,
-                            int32_t relu, void* stream) {
-  SCVAE_ARG(a && mean && var && beta && h && rows >= 0 && N > 0 && lda >= N && ldh >= N);
-  if (rows == 0) return 0;
-  return scvae::bn_apply((hipStream_t)stream, a, (int)lda, mean, var, (int)N, beta, h, (int)ldh,
-                         (int)rows, 1, (int)N, relu ? 1 : 0);
-}
-int scvae_bn_apply_relu_bwd(const float* dh, int64_t lddh, const float* h, int64_t ldh,
-                            const float* a, int64_t lda, const float* mean, const float* var,
-                            int64_t rows, int64_t N, int32_t relu, float* da, int64_t ldda,
-                            float* dbeta, float* workspace, void* stream) {
-  SCVAE_ARG(dh && h && a && mean && var && da && dbeta && workspace && rows > 0 && N > 0);
-  SCVAE_ARG(lddh >= N && ldh >= N && lda >= N && ldda >= N && rows <= INT32_MAX);
-  float* s1 = workspace;
-  float* s2 = workspace + N;
-  float* partial = workspace + 2 * N;
-  int rc = scvae::bn_bwd_stats((hipStream_t)stream, dh, (int)lddh, h, (int)ldh, a, (int)lda, mean,
-                               var, (int)rows, 1, (int)N, relu ? 1 : 0, s1, s2, partial, dbeta,
-                               nullptr, nullptr, rows);
-  if (rc) return rc;
-  return scvae::bn_bwd_apply((hipStream_t)stream, dh, (int)lddh, h, (int)ldh, a, (int)lda, mean,
-                             var, s1, s2, (int)rows, 1, (int)N, relu ? 1 : 0, 1.f / (float)rows,
-                             da, (int)ldda);
-}
-int scvae_softplus_gaussian_logprob_pair_fwd(const float* qm, const float* qs, const float* Wpm,
-                                             const float* bpm, const float* Wps,
-                                             const float* bps, const float* eps, float* z,
-                                             float* klz, float* qvar, int64_t K, int64_t S,
-                                             int64_t B, int64_t L, void* stream) {
-  SCVAE_ARG(K > 0 && S > 0 && B >= 0 && K <= 65535 && B <= INT32_MAX);
-  return scvae::softplus_gaussian_fwd((hipStream_t)stream, qm, qs, Wpm, bpm, Wps, bps, eps, z,
-                                      klz, qvar, (int)K, (int)S, (int)B, (int)L);
-}
-int scvae_softplus_gaussian_logprob_pair_bwd(const float* qm, const float* qs, const float* Wpm,
-                                             const float* bpm, const float* Wps,
-                                             const float* bps, const float* eps, const float* dz,
-                                             const float* gklz, float* dqm, float* dqs,
-                                             float* dprior, int64_t K, int64_t S, int64_t B,
-                                             int64_t L, void* stream) {
-  SCVAE_ARG(Wpm && bpm && Wps && bps && K > 0 && S > 0 && B >= 0 && L > 0);
-  return scvae::softplus_gaussian_bwd((hipStream_t)stream, qm, qs, Wpm, bpm, Wps, bps, eps, dz,
-                                      gklz, dqm, dqs, dprior, (int)K, (int)S, (int)B, (int)L);
-}
-int scvae_mvn_tril_logprob_pair_fwd(const float* qloc, const float* qscale, const float* Wpl,
-                                    const float* bpl, const float* Wps, const float* bps,
-                                    const float* eps, float* z, float* klz, float* qvar,
-                                    float* qcov, int64_t K, int64_t S, int64_t B, int64_t L,
-                                    void* stream) {
-  SCVAE_ARG(K > 0 && S > 0 && B >= 0 && L > 0 && L <= 64 && K <= 65535 && B <= INT32_MAX &&
-            S <= INT32_MAX);
-  return scvae::mvn_tril_fwd((hipStream_t)stream, qloc, qscale, Wpl, bpl, Wps, bps, eps, z, klz,
-                             qvar, qcov, (int)K, (int)S, (int)B, (int)L);
-}
-int scvae_mvn_tril_logprob_pair_bwd(const float* qloc, const float* qscale, const float* Wpl,
-                                    const float* bpl, const float* Wps, const float* bps,
-                                    const float* eps, const float* dz, const float* gklz,
-                                    float* dqloc, float* dqscale, float* dprior, int64_t K,
-                                    int64_t S, int64_t B, int64_t L, void* stream) {
-  SCVAE_ARG(K > 0 && S > 0 && B >= 0 && L > 0 && L <= 64 && K <= 65535 && B <= INT32_MAX &&
-            S <= INT32_MAX);
-  return scvae::mvn_tril_bwd((hipStream_t)stream, qloc, qscale, Wpl, bpl, Wps, bps, eps, dz, gklz,
-                             dqloc, dqscale, dprior, (int)K, (int)S, (int)B, (int)L);
-}
-int scvae_categorical_entropy_kl_fwd(const float* logits, float* y, float* kl_y_cell, int64_t B,
-                                     int64_t K, const float* prior_logits, void* stream) {
-  SCVAE_ARG(logits && y && kl_y_cell && B >= 0 && K > 0 && B <= INT32_MAX);
-  return scvae::categorical_fwd((hipStream_t)stream, logits, y, kl_y_cell, (int)B, (int)K,
-                                prior_logits);
-}
-int scvae_categorical_entropy_kl_bwd(const float* y, const float* dy, const float* gate, float c,
-                                     float* dlogits, int64_t B, int64_t K,
-                                     const float* prior_logits, void* stream) {
-  SCVAE_ARG(y && dy && gate && dlogits && B >= 0 && K > 0 && B <= INT32_MAX);
-  return scvae::categorical_bwd_gated((hipStream_t)stream, y, dy, gate, c, dlogits, (int)B,
-                                      (int)K, prior_logits);
-}
-int scvae_iw_logmeanexp(const float* ll, const float* kl_cell, int32_t kl_per_sample,
-                        int32_t n_iw, int32_t n_mc, int64_t B, float kl_weight, float row_scale,
-                        float* scalars, float* gw, void* stream) {
-  SCVAE_ARG(ll && kl_cell && scalars && n_iw > 0 && n_mc > 0 && B > 0 && B <= INT32_MAX);
-  return scvae::vae_elbo((hipStream_t)stream, ll, kl_cell, kl_per_sample ? 1 : 0, n_iw, n_mc,
-                         (int)B, kl_weight, row_scale, scalars, gw);
-}
-int scvae_pxmean_stats(int32_t kind, const float* const* pre, int64_t S, int64_t B, int64_t F,
-                       const float* weight, int64_t ldw, int32_t accumulate, float* p_x_mean,
-                       float* mean_of_var, float* var_of_mean, void* stream) {
-  SCVAE_ARG(pre && ((kind >= 0 && kind <= 3) || kind == LK_BERNOULLI) && S > 0 && B >= 0 && F > 0);
-  scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
-  for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = const_cast<float*>(pre[j]);
-  return scvae::px_statistics((hipStream_t)stream, kind, hp, (int)F, (int)S, (int)B, (int)F,
-                              weight, (int)ldw, accumulate ? 1 : 0, p_x_mean, mean_of_var,
-                              var_of_mean);
-}
-int scvae_philox_normal(float* out, int64_t rows, int64_t cols, int64_t row_offset, uint64_t seed,
-                        uint64_t stream_id, void* stream) {
-  return scvae::philox_normal((hipStream_t)stream, out, rows, (int)cols, row_offset, seed,
-                              stream_id);
-}
-int scvae_philox_normal_blocks(float* out, int64_t blocks, int64_t block_rows, int64_t cols,
-                               int64_t block_stride, int64_t row_offset, uint64_t seed,
-                               uint64_t stream_id, void* stream) {
-  SCVAE_ARG(blocks >= 0 && block_rows >= 0);
-  return scvae::philox_normal((hipStream_t)stream, out, blocks * block_rows, (int)cols, row_offset,
-                              seed, stream_id, block_rows, block_stride);
 }
 
 }  // extern "C"

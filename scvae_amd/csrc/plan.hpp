@@ -276,6 +276,77 @@ int build_gmvae(scvae_plan* p);
 size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t samples, bool dry);
 int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s);
 bool gm_tile_chain_ok(const scvae_plan* p, int B, int S, bool training);   // plan_gmvae.hip
+bool tile_chain_enabled();   // SCVAE_TILE_CHAIN (plan.hip)
+
+// The step path's one error-handling form: a launch or stage that fails ends the step with its
+// code.  GEMM: plan_gemm on the step's plan `p` and stream `s`.
+#define TRY(call)                      \
+  do {                                 \
+    if (int rc_ = (call)) return rc_;  \
+  } while (0)
+#define GEMM(...) TRY(plan_gemm(p, s, __VA_ARGS__))
+
+// ---- the tile-chain stages both steps are made of (plan.hip; kernels: tilechain.hip) ----
+// groups / group_rows: 1 / 0 for the VAE, K / rows per pass for the GMVAE's stacked passes
+TileBN tile_bn(scvae_plan* p, Dense& d, int groups, int group_rows, const float* part, int chunks,
+               int chunk, float* part_out);
+int tile_bn_forward(scvae_plan* p, hipStream_t s, Dense& d, int groups, int group_rows,
+                    const float* part, int chunks, int chunk, int rows, TileBN* out);
+int tile_bn_backward(scvae_plan* p, hipStream_t s, Dense& d, int groups, int group_rows,
+                     const float* part, int rows, float bessel, TileBN* out);
+// The chain of one step, on the step function's stack.  The dW / db slabs of the layers of a
+// backward pass wait for ONE fixed-order reduce at its end (they are not on the chain's critical
+// path: four launches fewer); slab buffer i <-> pending job i.  `record` (the VAE's resident /
+// segment variants; never the GMVAE): stages are collected in cf / cb and launched together.
+struct TileChain {
+  scvae_plan* p = nullptr;
+  hipStream_t s = nullptr;
+  int S = 1;                 // samples per cell (the barrier a recorded stage needs)
+  SlabJobs pending;
+  int sp = 0;                // ping-pong of the backward chunk sums (tc_spart)
+  bool record = false, resident = false;
+  int tiles = 0;             // 64-row tiles of a recorded launch
+  TileChainFwdArgs cf;
+  TileChainBwdArgs cb;
+  int cf_tiles = 0, cb_tiles = 0;
+};
+int tile_fwd_stage(TileChain& tc, const TileFwdArgs& q, int sync_after);
+int tile_fwd_flush(TileChain& tc);
+int tile_bwd_stage(TileChain& tc, const TileBwdArgs& q, int sync_after);
+int tile_bwd_flush(TileChain& tc);
+int tile_slab_flush(TileChain& tc);
+int tile_decoder_forward(TileChain& tc, std::vector<Dense>& dec, const float* dec_in, int L,
+                         int rows, int groups, int group_rows);
+int tile_layer_backward(TileChain& tc, Dense& d, Dense* below, const float* in, int rows,
+                        int groups, int group_rows, int64_t grows, const float* dh_in, float* d_in,
+                        float* dA_out);
+int tile_heads_backward(TileChain& tc, Dense& loc, Dense& scale, const float* dloc,
+                        const float* dscale, Dense& last, bool chain_below, int rows, int groups,
+                        int group_rows, int L, float* dh);
+
+// ---- the head stage both steps end their forward pass with (plan.hip) ----
+struct HeadPath {
+  bool training = false, head_drop = false, cpoisson = false;
+  bool fused = false;        // heads + likelihood (+ backward) in the fused kernels
+  bool fused_cat = false;    // -k, training: two launches of the bf16x9 head kernel
+  bool cat_forward = false;  // -k, forward only: two launches of decoder_forward_kernel
+  int n_fwd = 1, h1 = 0, KM = 0, ld = 0, R = 0, B = 0;
+  const float* dch = nullptr;            // the decoder's output [R, ld]
+  const float* head_in[4] = {};          // the heads' (dropped-out) inputs; [3]: the P_K head
+  HeadPtrs pre;
+  Targets tg;
+  HeadParams hp;
+};
+int head_path(scvae_plan* p, const scvae_step_args* a, hipStream_t s, bool training, int n_fwd,
+              const float* dch, int ld, int R, int B, HeadPath* out);
+int head_loglik_forward(scvae_plan* p, const scvae_step_args* a, hipStream_t s,
+                        const HeadPath& hd);
+int head_px_begin(scvae_plan* p, const scvae_step_args* a, hipStream_t s, const HeadPath& hd,
+                  bool* ll_done);
+int head_px_finish(scvae_plan* p, const scvae_step_args* a, hipStream_t s, const HeadPath& hd);
+int head_train(scvae_plan* p, const scvae_step_args* a, hipStream_t s, const HeadPath& hd,
+               float* dd);
+int head_backward(scvae_plan* p, hipStream_t s, const HeadPath& hd, float* dd, float* scratch);
 int plan_side_fork(scvae_plan* p, hipStream_t s, int point);   // scvae_step_args.side (plan.hip)
 int plan_side_finish(scvae_plan* p, hipStream_t s);
 }  // namespace scvae

@@ -242,12 +242,11 @@ size_t carve_gmvae(scvae_plan* p, void* base, size_t cap, int64_t cells, int64_t
 //      (scvae_plan_set_sync) the statistics of a layer are those of the global minibatch: the
 //      rank's chunks are merged per pass by a small kernel, the hook merges the ranks (the K
 //      passes' statistics in ONE collective, as the launch chain issues it), and the consuming
-//      tile kernel takes them as given -- gm_tile_bn_forward / gm_tile_bn_backward, the VAE's
-//      tile_bn_forward / tile_bn_backward (plan.hip) with groups. ----
+//      tile kernel takes them as given -- tile_bn_forward / tile_bn_backward (plan.hip) with
+//      groups. ----
 bool gm_tile_chain_ok(const scvae_plan* p, int B, int S, bool training) {
   const scvae_model_config& c = p->cfg;
-  static const bool env_on = [] { const char* e = getenv("SCVAE_TILE_CHAIN"); return !(e && e[0] == '0'); }();
-  if (!env_on || !p->use_tile_chain || !training || !c.batch_norm) return false;
+  if (!tile_chain_enabled() || !p->use_tile_chain || !training || !c.batch_norm) return false;
   if (p->zenc.empty() || p->xdec.empty() || c.decoder_extra != 0 || c.latent_size > 128) return false;
   if (B % 64 != 0 || ((int64_t)B * S) % 64 != 0) return false;
   for (const auto& d : p->zenc) if (d.n_out > 128 || !d.bn) return false;
@@ -255,84 +254,38 @@ bool gm_tile_chain_ok(const scvae_plan* p, int B, int S, bool training) {
   for (int i = 0; i < 4; ++i) if (dropout_keep(c, i) > 0.f) return false;
   return p->tc_part[0] != nullptr;
 }
-// the batch norm of layer d (K groups of `group_rows` rows) as the tile kernels see it
-static TileBN gm_tile_bn(scvae_plan* p, Dense& d, int K, int group_rows, const float* part,
-                         float* part_out) {
-  TileBN t;
-  const int N = d.n_out;
-  t.a = d.a; t.h = d.h; t.beta = p->params + d.beta;
-  t.mean = d.stats; t.var = d.stats + (size_t)K * N;
-  t.s1 = d.stats + 2 * (size_t)K * N; t.s2 = d.stats + 3 * (size_t)K * N;
-  t.part = part; t.chunks = K * (group_rows / 64); t.chunk = 64; t.part_out = part_out;
-  t.group_tiles = group_rows / 64; t.groups = K;
-  t.dbeta = p->grads ? p->grads + d.beta : nullptr;
-  t.mov_mean = p->moving + d.mov_mean; t.mov_var = p->moving + d.mov_var;
-  return t;
-}
 
-// the batch norm of layer d for the tile kernel that CONSUMES its forward statistics: merged by
-// that kernel from the chunk statistics `part` (single process), or -- data parallel -- merged
-// here per pass, over the ranks by the hook, and handed over as given
-static int gm_tile_bn_forward(scvae_plan* p, hipStream_t s, Dense& d, int K, int group_rows,
-                              const float* part, TileBN* out) {
-  if (!p->sync) {
-    *out = gm_tile_bn(p, d, K, group_rows, part, nullptr);
-    return 0;
-  }
-  const int N = d.n_out;
-  TileBN t = gm_tile_bn(p, d, K, group_rows, nullptr, nullptr);
-  int rc = tile_stats_merge(s, part, group_rows / 64, 64, group_rows, N, t.mean, t.var, K);
-  if (rc) return rc;
-  if (p->sync(p->sync_user, d.stats, 2 * (int64_t)K * N, 1, group_rows)) {
-    set_error("batch-norm sync hook failed");
-    return -2;
-  }
-  *out = t;
-  return 0;
-}
-// ... and for the tile kernel that consumes its backward sums (s1, s2: [K][N] behind mean / var)
-static int gm_tile_bn_backward(scvae_plan* p, hipStream_t s, Dense& d, int K, int group_rows,
-                               const float* part, float bessel, TileBN* out) {
-  if (!p->sync) {
-    *out = gm_tile_bn(p, d, K, group_rows, part, nullptr);
-    return 0;
-  }
-  const int N = d.n_out;
-  TileBN t = gm_tile_bn(p, d, K, group_rows, nullptr, nullptr);
-  int rc = tile_sums_merge(s, part, group_rows / 64, N, t, bessel, K);
-  if (rc) return rc;
-  if (p->sync(p->sync_user, t.s1, 2 * (int64_t)K * N, 0, group_rows)) {
-    set_error("batch-norm backward sync hook failed");
-    return -2;
-  }
-  *out = t;
-  return 0;
-}
+// One GMVAE step: the values its stages share, on gmvae_step's stack.  The stages are member
+// functions so that they read those values by name; nothing here is virtual or allocated.
+struct GmStep {
+  scvae_plan* p; const scvae_step_args* a; hipStream_t s;
+  int K, B, S, KB, SB, R, F, L;
+  int Ls;          // width of the scale heads: L, or the L (L + 1) / 2 triangle entries
+  bool fullcov, training, tile;
+  int64_t GB;
+  float w, inv_gb;
+  const float* prior = nullptr;                 // K logits of p(y), or nullptr: uniform
+  const float* hy = nullptr; int ldy = 0;       // the (dropped-out) input of the q(y|x) logits
+  const float *hz_m = nullptr, *hz_s = nullptr; // ... of the two q(z|x,y) heads
+  const float *Wpm, *bpm, *Wps, *bps;           // p(z|y): (row-scaled) weights, biases
+  bool prior_drop = false;
+  const float* dec_in = nullptr;   // decoder input: z_k, or [z_k | extra] (gm:3094-3130)
+  float* gate = nullptr;
+  float share = 1.f;               // this rank's share of the global minibatch
+  TileChain tc;                    // (never recording: a launch per stage)
 
-int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
-  const scvae_model_config& c = p->cfg;
-  const int K = c.n_clusters, B = (int)a->cells, S = a->n_iw * a->n_mc;
-  const int KB = K * B, SB = S * B, R = K * SB;
-  const int F = c.feature_size, L = c.latent_size;
-  // full-covariance mixture: the scale heads hold the Ls = L (L + 1) / 2 triangle entries
-  const bool fullcov = (c.latent_mode & 8) != 0;
-  const int Ls = p->qscale.n_out;
-  const bool training = a->training != 0;
-  const int64_t GB = a->global_cells > 0 ? a->global_cells : a->cells;
-  const float w = a->warm_up_weight * c.kl_weight;
-  const float inv_gb = 1.f / (float)GB;
-  int rc;
-  p->drop_seed = a->dropout_seed;
-#define GEMM(...)                                                              \
-  do {                                                                         \
-    if ((rc = plan_gemm(p, s, __VA_ARGS__))) return rc;                        \
-  } while (0)
-#define TRY(call)                  \
-  do {                             \
-    if ((rc = (call))) return rc;  \
-  } while (0)
+  int forward_qy();
+  int forward_qz();
+  int latent();
+  int backward_decoder(float* dcur, float* dalt);
+  int backward_latent();
+  int backward_qz();
+  int backward_qy();
+  int step();
+};
 
-  // ---------------- q(y|x) (gm:3050-3092) ----------------
+// ---------------- q(y|x) (gm:3050-3092) ----------------
+int GmStep::forward_qy() {
   // (the fp32 batch, or the token of the uint16 one: plan_gemm hands that to the count kernels)
   const float* h = p->step_x;
   int ld = F;
@@ -340,17 +293,18 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     TRY(dense_forward(p, s, d, h, ld, B, 1, true, training));
     h = d.h; ld = d.n_out;
   }
-  const float* hy = h;
-  int ldy = ld;
+  hy = h; ldy = ld;
   TRY(dense_input(p, s, p->ylogits, h, ld, B, training, &hy, &ldy));
   GEMM(false, false, hy, p->params + p->ylogits.w, p->params + p->ylogits.b, p->logits, B, K,
        p->ylogits.n_in, ldy, K, K, ACT_NONE, false);
-  const float* prior = p->prior_off != NPOS ? p->params + p->prior_off : nullptr;
+  prior = p->prior_off != NPOS ? p->params + p->prior_off : nullptr;
   TRY(categorical_fwd(s, p->logits, p->yprob, p->kl_y_cell, B, K, prior));
   if (a->q_y_logits) TRY(copy(s, p->logits, a->q_y_logits, (size_t)B * K));
+  return 0;
+}
 
-  // ---------------- q(z|x,y=k), all k (gm:2936-3007) ----------------
-  const bool tile = gm_tile_chain_ok(p, B, S, training);
+// ---------------- q(z|x,y=k), all k (gm:2936-3007) ----------------
+int GmStep::forward_qz() {
   int tcur = 0;     // (ping-pong of the tile chain's chunk statistics)
   const float* hz = p->step_x;
   int ldz = F;
@@ -395,7 +349,7 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
       TileFwdArgs q;
       q.rows = KB; q.K = d.n_in;
       if (i == 1) { q.x = p->zenc[0].h; q.ldx = d.n_in; }
-      else TRY(gm_tile_bn_forward(p, s, p->zenc[i - 1], K, B, p->tc_part[tcur], &q.bn));
+      else TRY(tile_bn_forward(p, s, p->zenc[i - 1], K, B, p->tc_part[tcur], 0, 0, 0, &q.bn));
       q.n_out = 1;
       q.o[0].W = p->params + d.w; q.o[0].b = p->params + d.b; q.o[0].out = d.a;
       q.o[0].part = p->tc_part[i == 1 ? tcur : tcur ^ 1]; q.o[0].N = d.n_out;
@@ -410,8 +364,7 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     set_error("GMVAE needs at least one hidden layer");
     return -1;
   }
-  const float* hz_m = hz;
-  const float* hz_s = hz;
+  hz_m = hz_s = hz;
   int ldz_m = ldz, ldz_s = ldz;
   if (tile && fullcov) {
     // the scale head is wider than the tile kernels' heads: the last layer's normalisation alone,
@@ -419,7 +372,7 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     if (p->zenc.size() > 1) {
       TileFwdArgs q;
       q.rows = KB; q.K = p->zenc.back().n_out;
-      TRY(gm_tile_bn_forward(p, s, p->zenc.back(), K, B, p->tc_part[tcur], &q.bn));
+      TRY(tile_bn_forward(p, s, p->zenc.back(), K, B, p->tc_part[tcur], 0, 0, 0, &q.bn));
       TRY(tile_forward(s, q));
     }
     GEMM(false, false, hz, p->params + p->qmean.w, p->params + p->qmean.b, p->qm, KB, L,
@@ -431,7 +384,7 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     TileFwdArgs q;
     q.rows = KB; q.K = p->zenc.back().n_out;
     if (p->zenc.size() == 1) { q.x = p->zenc[0].h; q.ldx = q.K; }
-    else TRY(gm_tile_bn_forward(p, s, p->zenc.back(), K, B, p->tc_part[tcur], &q.bn));
+    else TRY(tile_bn_forward(p, s, p->zenc.back(), K, B, p->tc_part[tcur], 0, 0, 0, &q.bn));
     q.n_out = 2;
     q.o[0].W = p->params + p->qmean.w; q.o[0].b = p->params + p->qmean.b; q.o[0].out = p->qm;
     q.o[0].N = L;
@@ -439,20 +392,23 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     q.o[1].N = L;
     TRY(tile_forward(s, q));
   } else {
-  TRY(dense_input(p, s, p->qmean, hz, ldz, KB, training, &hz_m, &ldz_m));
-  TRY(dense_input(p, s, p->qscale, hz, ldz, KB, training, &hz_s, &ldz_s));
-  GEMM(false, false, hz_m, p->params + p->qmean.w, p->params + p->qmean.b, p->qm, KB, L,
-       p->qmean.n_in, ldz_m, L, L, ACT_NONE, false);
-  GEMM(false, false, hz_s, p->params + p->qscale.w, p->params + p->qscale.b, p->qs, KB, Ls,
-       p->qscale.n_in, ldz_s, Ls, Ls, ACT_NONE, false);
+    TRY(dense_input(p, s, p->qmean, hz, ldz, KB, training, &hz_m, &ldz_m));
+    TRY(dense_input(p, s, p->qscale, hz, ldz, KB, training, &hz_s, &ldz_s));
+    GEMM(false, false, hz_m, p->params + p->qmean.w, p->params + p->qmean.b, p->qm, KB, L,
+         p->qmean.n_in, ldz_m, L, L, ACT_NONE, false);
+    GEMM(false, false, hz_s, p->params + p->qscale.w, p->params + p->qscale.b, p->qs, KB, Ls,
+         p->qscale.n_in, ldz_s, Ls, Ls, ACT_NONE, false);
   }
-  const float* Wpm = p->params + p->pmean.w;
-  const float* bpm = p->params + p->pmean.b;
-  const float* Wps = p->params + p->pscale.w;
-  const float* bps = p->params + p->pscale.b;
+  return 0;
+}
+
+// ---------------- p(z|y), the latent stage and its statistics ----------------
+int GmStep::latent() {
+  Wpm = p->params + p->pmean.w; bpm = p->params + p->pmean.b;
+  Wps = p->params + p->pscale.w; bps = p->params + p->pscale.b;
   // p(z|y=k): a dense layer on the one-hot (gm:3009-3048); its dropout keeps or drops the one
   // non-zero input of pass k, i.e. scales row k of the weights
-  const bool prior_drop = training && p->pmean.keep > 0.f;
+  prior_drop = training && p->pmean.keep > 0.f;
   if (prior_drop) {
     TRY(dropout_scale_rows(s, Wpm, p->pmean.in_drop, K, L, p->pmean.keep, p->drop_seed,
                            p->pmean.site));
@@ -467,8 +423,8 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     TRY(mvn_tril_fwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->z, p->klz, qvar, qcov, K, S, B,
                      L));
   else
-  TRY(softplus_gaussian_fwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->z, p->klz, qvar, K, S,
-                            B, L));
+    TRY(softplus_gaussian_fwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->z, p->klz, qvar, K,
+                              S, B, L));
   if (a->q_z_mean)  // z_mean = sum_k y_k mean_k (gm:2895-2899)
     TRY(sum_groups(s, p->qm, p->yprob, K, K, B, L, a->q_z_mean));
   if (a->cluster_stats) {
@@ -476,7 +432,7 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     if (fullcov)
       TRY(mvn_tril_prior_stats(s, Wpm, bpm, Wps, bps, K, L, cs, cs + (size_t)K * L, nullptr));
     else
-    TRY(prior_stats(s, Wpm, bpm, Wps, bps, K, L, cs, cs + (size_t)K * L));
+      TRY(prior_stats(s, Wpm, bpm, Wps, bps, K, L, cs, cs + (size_t)K * L));
     // q_z_means / q_z_variances: this rank's share of the batch means (gm:2884-2887)
     TRY(group_col_sum(s, p->qm, L, B, K, L, inv_gb, cs + 2 * (size_t)K * L, p->partial));
     TRY(group_col_sum(s, qvar, L, B, K, L, inv_gb, cs + 3 * (size_t)K * L, p->partial));
@@ -490,255 +446,46 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
                              p->sum_scratch + (size_t)K * L, cc));
     TRY(group_col_sum(s, qcov, L * L, B, K, L * L, inv_gb, cc + KLL, p->partial));
   }
+  return 0;
+}
 
-  // ---------------- decoder p(x|z_k), all k (gm:3094-3221) ----------------
-  const int E = c.decoder_extra;
-  const float* dec_in = p->z;   // decoder input: z_k, or [z_k | extra] (gm:3094-3130)
-  if (E > 0) {
-    TRY(concat_extra(s, p->z, L, a->decoder_extra, E, (size_t)R, (size_t)B, p->zcat));
-    dec_in = p->zcat;
-  }
-  const float* dch = dec_in;
-  ld = L + E;
-  if (tile) {
-    int cur = 0;
-    for (size_t i = 0; i <= p->xdec.size(); ++i) {
-      TileFwdArgs q;
-      q.rows = R;
-      if (i == 0) { q.x = dec_in; q.ldx = L; q.K = L; }
-      else {
-        q.K = p->xdec[i - 1].n_out;
-        TRY(gm_tile_bn_forward(p, s, p->xdec[i - 1], K, SB, p->tc_part[cur], &q.bn));
-      }
-      if (i < p->xdec.size()) {
-        Dense& d = p->xdec[i];
-        q.n_out = 1;
-        q.o[0].W = p->params + d.w; q.o[0].b = p->params + d.b; q.o[0].out = d.a;
-        q.o[0].part = p->tc_part[i == 0 ? cur : cur ^ 1]; q.o[0].N = d.n_out;
-      }   // (i == size: the last layer's normalisation alone -> its h feeds the likelihood heads)
-      TRY(tile_forward(s, q));
-      if (i > 0) cur ^= 1;
-    }
-    dch = p->xdec.back().h; ld = p->xdec.back().n_out;
-  } else {
-  for (auto& d : p->xdec) {
-    TRY(dense_forward(p, s, d, dch, ld, R, K, true, training));
-    dch = d.h; ld = d.n_out;
-  }
-  }
-  HeadPtrs pre;
-  for (int j = 0; j < 3; ++j) pre.p[j] = p->pre[j];
-  const int h1 = p->heads[0].n_in;
-  // fused heads + likelihood (+ backward) unless the evaluate-time statistics are requested
-  const int KM = c.k_max, FC = F * (KM + 1);   // piecewise categorical likelihood: unfused path
-  // (dropout: every head draws its own mask of the decoder output: the bf16x9 kernel's DROP
-  //  instantiation, or the unfused path)
-  const bool head_drop = training && p->heads[0].keep > 0.f;
-  // row softmax: three passes of the bf16x9 head kernel (decoder_fused_cpoisson), or unfused
-  const bool cpoisson = c.likelihood == LK_CPOISSON;
-  if (cpoisson && !a->count_sum) {
-    set_error("the constrained Poisson likelihood needs scvae_step_args.count_sum");
-    return -1;
-  }
-  const bool fused_width =
-      decoder_fused_supported(h1) ||
-      (!head_drop && !cpoisson && decoder_fused_train_supported(p->P, h1, p->head_arith));
-  const bool fused = p->use_fused && p->fused_ws && fused_width && ld == h1 &&
-                     !a->p_x_mean && KM == 0 &&
-                     (!head_drop || (heads_fused_dropout_ok(p, 1) && !cpoisson)) &&
-                     (c.likelihood <= LK_ZINB || c.likelihood == LK_BERNOULLI ||
-                      (cpoisson && decoder_fused_cpoisson_supported(h1, p->head_arith)));
-  if (p->x_u16 && !fused) {
-    set_error("the uint16 minibatch needs the fused likelihood kernels (no -k / constrained "
-              "Poisson, evaluation statistics, or head dropout outside the bf16x9 kernel)");
-    return -1;
-  }
-  // the K stacked passes read the same targets (row r uses t[r % B]): as uint16 they are half
-  // the bytes of every pass
-  const Targets tg = p->x_u16 ? targets_u16(p->step_u16, p->step_u16_ld) : targets_f32(a->t, F);
-  const HeadParams hp = head_params(p);
-  // -k (k = 1, 2) in a training step: two launches of the bf16x9 head kernel over the K stacked
-  // passes (decoder_fused_train_cat, see plan.hip)
-  const bool fused_cat = training && KM > 0 && p->use_fused && p->fused_ws && p->pre_k &&
-                         ld == h1 && !head_drop && !p->x_u16 && !a->p_x_mean &&
-                         decoder_fused_cat_supported(c.likelihood, KM, h1, p->head_arith);
-  const bool cat_forward = !training && KM > 0 && p->use_fused && p->fused_ws && p->pre_k &&
-                           ld == h1 && !p->x_u16 && !a->p_x_mean &&
-                           decoder_fused_forward_cat_supported(c.likelihood, KM, h1);
-  const float* head_in[4] = {dch, dch, dch, dch};   // [3]: the P_K head
-  if (!fused && !fused_cat && !cat_forward)
-    TRY(heads_forward(p, s, dch, ld, R, training, head_in));
-  bool ll_done = false;
-  if (a->p_x_mean) {
-    if (!(a->p_x_stddev && a->stddev_of_p_x_given_z_mean)) {
-      set_error("p_x_mean requires p_x_stddev and stddev_of_p_x_given_z_mean");
-      return -1;
-    }
-    if (cpoisson) {   // likelihood of the logits first, then rates in place for the statistics
-      if (training) {
-        set_error("p_x_mean in a training step of the constrained Poisson likelihood");
-        return -1;
-      }
-      TRY(cpoisson_fwd(s, a->t, F, p->pre[0], F, a->count_sum, a->row_const, p->ll, R, B, F));
-      ll_done = true;
-      TRY(cpoisson_rate(s, p->pre[0], F, a->count_sum, R, B, F));
-    }
-    for (int k = 0; k < K; ++k) {
-      HeadPtrs pk;
-      for (int j = 0; j < 3; ++j)
-        pk.p[j] = p->pre[j] ? p->pre[j] + (size_t)k * SB * F : nullptr;
-      if (KM > 0)
-        TRY(px_statistics_cat(s, c.likelihood, pk, F, p->pre_k + (size_t)k * SB * FC, KM, S, B, F,
-                              p->yprob + k, K, k > 0 ? 1 : 0, a->p_x_mean, p->mov, p->vom));
-      else
-        TRY(px_statistics(s, c.likelihood, pk, F, S, B, F, p->yprob + k, K, k > 0 ? 1 : 0,
-                          a->p_x_mean, p->mov, p->vom));
-    }
-    TRY(sqrt_sum(s, p->vom, p->mov, a->p_x_stddev, (size_t)B * F));
-    TRY(sqrt_sum(s, p->vom, nullptr, a->stddev_of_p_x_given_z_mean, (size_t)B * F));
-  }
-
-  // ---------------- loss (gm:3223-3410) ----------------
-  float* sums = p->kl_cell + B;     // 3 floats (+ gate at [8])
-  float* gate = sums + 8;
-  const float p_y_entropy = logf((float)K);
-  const float thr = c.free_nats_proportion * p_y_entropy;
-  const int use_free_nats = c.free_nats_proportion != 0.f;
-  if (!training) {
-    if (fused && cpoisson)
-      TRY(decoder_fused_cpoisson(s, false, dch, R, h1, hp, F, tg, B, nullptr, a->count_sum,
-                                 a->row_const, p->ll, nullptr, p->fused_ws));
-    else if (fused)
-      TRY(decoder_fused_forward(s, c.likelihood, dch, R, h1, hp, F, tg, B, a->row_const, p->ll,
-                                p->fused_ws, p->head_arith));
-    else if (cat_forward)
-      TRY(decoder_fused_forward_cat(s, c.likelihood, KM, dch, R, h1, hp, p->params + p->head_k.w,
-                                    p->params + p->head_k.b, F, a->t, B, p->ll, p->fused_ws,
-                                    p->pre_k));
-    else if (KM > 0)
-      TRY(loglik_cat_fwd(s, c.likelihood, a->t, F, pre, F, p->pre_k, KM, p->ll, R, B, F));
-    else if (cpoisson) {
-      if (!ll_done)
-        TRY(cpoisson_fwd(s, a->t, F, p->pre[0], F, a->count_sum, a->row_const, p->ll, R, B, F));
-    } else
-      TRY(loglik_fwd(s, c.likelihood, a->t, F, pre, F, a->row_const, p->ll, R, B, F));
-    TRY(gmvae_elbo(s, p->ll, p->klz, p->yprob, p->kl_y_cell, K, S, B, inv_gb, sums, nullptr));
-    TRY(gmvae_elbo_finish(s, sums, w, thr, use_free_nats, 1.f, a->scalars, gate, prior, K,
-                          c.free_nats_proportion));
-    if (a->log_p_x_given_z) TRY(copy(s, p->ll, a->log_p_x_given_z, (size_t)R));
-    return 0;
-  }
-  // d(-ELBO_w)/d log p(t|z_k)[k,s,b] = -y[b,k]/(S*GB): known before the likelihood pass
-  TRY(gmvae_elbo_bwd(s, p->klz, p->klz, p->yprob, gate, K, S, B, w, inv_gb, p->gw, p->gklz,
-                     p->dy));  // (fills gw, gklz; dy is recomputed below with ll)
-  float* dcur = p->dbuf[0];
-  float* dalt = p->dbuf[1];
+// ---------------- backward: decoder ----------------
+int GmStep::backward_decoder(float* dcur, float* dalt) {
+  const int E = p->cfg.decoder_extra;
   float* scratch = p->dbuf[2];
-  if (fused) {
-    HeadDropout hdrop;
-    if (head_drop) TRY(heads_dropout_inputs(p, s, dch, ld, R, &hdrop));
-    if (cpoisson)
-      TRY(decoder_fused_cpoisson(s, true, dch, R, h1, hp, F, tg, B, p->gw, a->count_sum,
-                                 a->row_const, p->ll, dcur, p->fused_ws));
-    else
-      TRY(decoder_fused_train(s, c.likelihood, dch, R, h1, hp, F, tg, B, p->gw, a->row_const,
-                              p->ll, dcur, p->fused_ws, p->head_arith, false,
-                              head_drop ? &hdrop : nullptr, p->dd_atomics));
-  } else if (fused_cat) {
-    Dense& hk = p->head_k;
-    TRY(decoder_fused_train_cat(s, c.likelihood, KM, dch, R, h1, hp, p->params + hk.w,
-                                p->params + hk.b, p->grads + hk.w, p->grads + hk.b, F, a->t, B,
-                                p->gw, p->ll, dcur, p->fused_ws, p->head_arith, p->pre_k));
-  } else if (KM > 0) {
-    TRY(loglik_cat_bwd(s, c.likelihood, a->t, F, pre, F, p->pre_k, KM, p->gw, p->ll, R, B, F));
-  } else if (cpoisson) {
-    TRY(cpoisson_bwd(s, a->t, F, p->pre[0], F, p->gw, a->count_sum, a->row_const, p->ll, R, B, F));
-  } else {
-    TRY(loglik_bwd(s, c.likelihood, a->t, F, pre, F, p->gw, a->row_const, p->ll, R, B, F));
-  }
-  TRY(gmvae_elbo(s, p->ll, p->klz, p->yprob, p->kl_y_cell, K, S, B, inv_gb, sums, nullptr));
-  float share = 1.f;
-  if (p->sync) {
-    // the free-nats gate depends on the global kl_divergence_y
-    if (p->sync(p->sync_user, sums, 3, 0, B)) {
-      set_error("ELBO sync hook failed");
-      return -2;
-    }
-    share = (float)a->cells / (float)GB;
-  }
-  TRY(gmvae_elbo_finish(s, sums, w, thr, use_free_nats, share, a->scalars, gate, prior, K,
-                        c.free_nats_proportion));
-  TRY(gmvae_elbo_bwd(s, p->ll, p->klz, p->yprob, gate, K, S, B, w, inv_gb, p->gw, p->gklz, p->dy));
-  if (a->log_p_x_given_z) TRY(copy(s, p->ll, a->log_p_x_given_z, (size_t)R));
-
-  // ---------------- backward: heads + decoder ----------------
-  if (!fused && !fused_cat) TRY(heads_backward(p, s, head_in, R, head_drop, dcur, dalt));
-  // the next minibatch and its noise (scvae_step_args.side) under the rest of the backward pass
-  TRY(plan_side_fork(p, s, 1));
   const int64_t GSB = GB * S;  // global rows per group (pass) in the decoder
-  // (tile chain) the dW / db slabs of the layers wait for one fixed-order reduce at the end
-  SlabJobs pending;
-  int sp = 0;
-  auto bessel = [](int64_t n) { return (float)n / (float)(n > 1 ? n - 1 : 1); };
-  auto flush = [&]() -> int {
-    if (pending.n_jobs == 0) return 0;
-    const int r = tile_slab_reduce(s, pending);
-    pending.n_jobs = 0;
-    return r;
-  };
-  // one batch-normalised layer backwards: its own sums merged per group, dA, d_in, its dW slab and
-  // the chunk sums of the layer below
-  auto tile_layer_backward = [&](Dense& d, Dense* below, const float* in, int rows, int group_rows,
-                                 int64_t grows, const float* dh_in, float* d_in) -> int {
-    TileBwdArgs q;
-    const int G = rows / 64;
-    q.rows = rows; q.inv_count = 1.f / (float)grows; q.bessel = bessel(grows);
-    q.n_up = 1;
-    if (pending.n_jobs == TC_MAX_JOBS) { const int r = flush(); if (r) return r; }
-    float* slab = p->tc_slab[pending.n_jobs % TC_MAX_JOBS];
-    q.up[0].g = dh_in; q.up[0].W = p->params + d.w; q.up[0].N = d.n_out;
-    q.up[0].dW_slab = slab;
-    {
-      const int r = gm_tile_bn_backward(p, s, d, K, group_rows, p->tc_spart[sp], q.bessel, &q.bn);
-      if (r) return r;
-    }
-    q.in = in; q.K = d.n_in; q.d_in = d_in;
-    if (below) q.below = gm_tile_bn(p, *below, K, group_rows, nullptr, p->tc_spart[sp ^ 1]);
-    const int r = tile_backward(s, q);
-    if (r) return r;
-    pending.job[pending.n_jobs++] = {slab, p->grads + d.w, d.n_in * d.n_out, G};
-    sp ^= 1;
-    return 0;
-  };
   if (tile) {
     Dense& top = p->xdec.back();
-    TRY(tile_backward_stats(s, dcur, gm_tile_bn(p, top, K, SB, nullptr, p->tc_spart[sp]), R,
+    TRY(tile_backward_stats(s, dcur, tile_bn(p, top, K, SB, nullptr, 0, 0, p->tc_spart[tc.sp]), R,
                             top.n_out));
     for (int i = (int)p->xdec.size() - 1; i >= 0; --i) {
       const float* in = i > 0 ? p->xdec[i - 1].h : dec_in;
       float* d_in = i > 0 ? dalt : p->dz;
-      TRY(tile_layer_backward(p->xdec[i], i > 0 ? &p->xdec[i - 1] : nullptr, in, R, SB, GSB, dcur,
-                              d_in));
+      TRY(tile_layer_backward(tc, p->xdec[i], i > 0 ? &p->xdec[i - 1] : nullptr, in, R, K, SB, GSB,
+                              dcur, d_in, nullptr));
       if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
     }
   } else {
-  for (int i = (int)p->xdec.size() - 1; i >= 0; --i) {
-    Dense& d = p->xdec[i];
-    const float* in = i > 0 ? p->xdec[i - 1].h : dec_in;
-    float* d_in = i > 0 ? dalt : (E > 0 ? p->dzcat : p->dz);
-    TRY(dense_backward(p, s, d, in, d.n_in, R, K, true, dcur, scratch, d_in, false, GSB));
-    if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
-  }
+    for (int i = (int)p->xdec.size() - 1; i >= 0; --i) {
+      Dense& d = p->xdec[i];
+      const float* in = i > 0 ? p->xdec[i - 1].h : dec_in;
+      float* d_in = i > 0 ? dalt : (E > 0 ? p->dzcat : p->dz);
+      TRY(dense_backward(p, s, d, in, d.n_in, R, K, true, dcur, scratch, d_in, false, GSB));
+      if (i > 0) { float* t = dcur; dcur = dalt; dalt = t; }
+    }
   }
   if (E > 0 && !p->xdec.empty()) TRY(slice_cols(s, p->dzcat, L + E, L, (size_t)R, p->dz));
+  return 0;
+}
 
-  // ---------------- backward: latent, prior, q(z|x,y) ----------------
+// ---------------- backward: latent, prior ----------------
+int GmStep::backward_latent() {
   if (fullcov)
     TRY(mvn_tril_bwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->dz, p->gklz, p->dqm, p->dqs,
                      p->dprior, K, S, B, L));
   else
-  TRY(softplus_gaussian_bwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->dz, p->gklz, p->dqm,
-                            p->dqs, p->dprior, K, S, B, L));
+    TRY(softplus_gaussian_bwd(s, p->qm, p->qs, Wpm, bpm, Wps, bps, a->eps, p->dz, p->gklz, p->dqm,
+                              p->dqs, p->dprior, K, S, B, L));
   // prior dense layers on the one-hot: dW[k,:] = sum_b, db = sum_k dW[k,:]
   const int LP = L + Ls;   // row of dprior: (d pm | d ps)
   TRY(group_col_sum(s, p->dprior, LP, B, K, LP, 1.f, p->sum_scratch, p->partial));
@@ -757,58 +504,45 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
       TRY(dropout_scale_rows(s, dWps, dWps, K, Ls, p->pscale.keep, p->drop_seed, p->pscale.site));
     }
   }
+  return 0;
+}
+
+// ---------------- backward: q(z|x,y) ----------------
+int GmStep::backward_qz() {
+  float* scratch = p->dbuf[2];
   float* dh = p->dbuf[0];
   float* dh_alt = p->dbuf[1];
   if (tile && !fullcov) {
     // the two posterior heads: dW, db of both, dh of the last q(z|x,y) layer and (where that
     // layer belongs to the chain) its chunk sums
-    Dense& last = p->zenc.back();
-    const int G = KB / 64, Kl = last.n_out;
-    if (pending.n_jobs + 4 > TC_MAX_JOBS) TRY(flush());
-    float* slab2[2] = {p->tc_slab[pending.n_jobs], p->tc_slab[pending.n_jobs + 1]};
-    TileBwdArgs q;
-    q.rows = KB; q.n_up = 2;
-    for (int u = 0; u < 2; ++u) {
-      Dense& hd = u == 0 ? p->qmean : p->qscale;
-      q.up[u].g = u == 0 ? p->dqm : p->dqs;
-      q.up[u].W = p->params + hd.w; q.up[u].N = L;
-      q.up[u].dW_slab = slab2[u];
-      q.up[u].db_slab = slab2[u] + (size_t)G * 128 * 128;
-    }
-    q.in = last.h; q.K = Kl; q.d_in = dh;
-    if (p->zenc.size() > 1) q.below = gm_tile_bn(p, last, K, B, nullptr, p->tc_spart[sp]);
-    TRY(tile_backward(s, q));
-    const int j0 = pending.n_jobs;
-    pending.job[j0] = {slab2[0], p->grads + p->qmean.w, Kl * L, G};
-    pending.job[j0 + 1] = {slab2[1], p->grads + p->qscale.w, Kl * L, G};
-    pending.job[j0 + 2] = {q.up[0].db_slab, p->grads + p->qmean.b, L, G};
-    pending.job[j0 + 3] = {q.up[1].db_slab, p->grads + p->qscale.b, L, G};
-    pending.n_jobs = j0 + 4;
+    TRY(tile_heads_backward(tc, p->qmean, p->qscale, p->dqm, p->dqs, p->zenc.back(),
+                            p->zenc.size() > 1, KB, K, B, L, dh));
   } else {
-  for (int q = 0; q < 2; ++q) {
-    Dense& hd = q == 0 ? p->qmean : p->qscale;
-    const float* dpre = q == 0 ? p->dqm : p->dqs;
-    const float* hq = q == 0 ? hz_m : hz_s;   // the (dropped-out) input of that layer
-    const bool drop = hd.keep > 0.f;
-    const int N = hd.n_out;   // L, or Ls for the scales of the full-covariance mixture
-    GEMM(true, false, hq, dpre, nullptr, p->grads + hd.w, hd.n_in, N, KB, hd.n_in, N, N, ACT_NONE,
-         false);
-    TRY(col_sum(s, dpre, N, KB, N, p->grads + hd.b, 1.f, 0, p->partial));
-    GEMM(false, true, dpre, p->params + hd.w, nullptr, drop ? dh_alt : dh, KB, hd.n_in, N, N, N,
-         hd.n_in, ACT_NONE, !drop && q > 0);
-    if (drop) TRY(dense_input_backward(p, s, hd, dh_alt, dh, KB, q > 0));
-  }
-  // (full covariance on the tile chain: the heads ran as GEMMs; the chain's next kernel wants the
-  //  chunk sums of the last q(z|x,y) layer's batch-norm backward, as the decoder's top layer)
-  if (tile && p->zenc.size() > 1)
-    TRY(tile_backward_stats(s, dh, gm_tile_bn(p, p->zenc.back(), K, B, nullptr, p->tc_spart[sp]),
-                            KB, p->zenc.back().n_out));
+    for (int q = 0; q < 2; ++q) {
+      Dense& hd = q == 0 ? p->qmean : p->qscale;
+      const float* dpre = q == 0 ? p->dqm : p->dqs;
+      const float* hq = q == 0 ? hz_m : hz_s;   // the (dropped-out) input of that layer
+      const bool drop = hd.keep > 0.f;
+      const int N = hd.n_out;   // L, or Ls for the scales of the full-covariance mixture
+      GEMM(true, false, hq, dpre, nullptr, p->grads + hd.w, hd.n_in, N, KB, hd.n_in, N, N, ACT_NONE,
+           false);
+      TRY(col_sum(s, dpre, N, KB, N, p->grads + hd.b, 1.f, 0, p->partial));
+      GEMM(false, true, dpre, p->params + hd.w, nullptr, drop ? dh_alt : dh, KB, hd.n_in, N, N, N,
+           hd.n_in, ACT_NONE, !drop && q > 0);
+      if (drop) TRY(dense_input_backward(p, s, hd, dh_alt, dh, KB, q > 0));
+    }
+    // (full covariance on the tile chain: the heads ran as GEMMs; the chain's next kernel wants the
+    //  chunk sums of the last q(z|x,y) layer's batch-norm backward, as the decoder's top layer)
+    if (tile && p->zenc.size() > 1)
+      TRY(tile_backward_stats(s, dh, tile_bn(p, p->zenc.back(), K, B, nullptr, 0, 0,
+                                             p->tc_spart[tc.sp]),
+                              KB, p->zenc.back().n_out));
   }
   for (int i = (int)p->zenc.size() - 1; i >= 0; --i) {
     Dense& d = p->zenc[i];
     if (i > 0 && tile) {
-      TRY(tile_layer_backward(d, i > 1 ? &p->zenc[i - 1] : nullptr, p->zenc[i - 1].h, KB, B, GB,
-                              dh, dh_alt));
+      TRY(tile_layer_backward(tc, d, i > 1 ? &p->zenc[i - 1] : nullptr, p->zenc[i - 1].h, KB, K, B,
+                              GB, dh, dh_alt, nullptr));
       float* t = dh; dh = dh_alt; dh_alt = t;
     } else if (i > 0) {
       TRY(dense_backward(p, s, d, p->zenc[i - 1].h, d.n_in, KB, K, true, dh, scratch, dh_alt,
@@ -828,14 +562,21 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
         TRY(group_col_sum(s, da, N, B, K, N, 1.f, dW + (size_t)F * N, p->partial));
         // data rows: dW[:F] = x^T (sum_k dA[k])
         TRY(sum_groups(s, da, nullptr, 0, K, B, N, p->sum_scratch));
-        GEMM(true, false, p->step_x, p->sum_scratch, nullptr, dW, F, N, B, F, N, N, ACT_NONE, false);
+        GEMM(true, false, p->step_x, p->sum_scratch, nullptr, dW, F, N, B, F, N, N, ACT_NONE,
+             false);
       }
     }
   }
+  // (the weight-gradient slabs of the chain: one fixed-order reduce)
+  if (tile) TRY(tile_slab_flush(tc));
+  return 0;
+}
 
-  if (tile) TRY(flush());     // (the weight-gradient slabs of the chain: one fixed-order reduce)
-
-  // ---------------- backward: q(y|x) ----------------
+// ---------------- backward: q(y|x) ----------------
+int GmStep::backward_qy() {
+  const scvae_model_config& c = p->cfg;
+  float* scratch = p->dbuf[2];
+  float *dh, *dh_alt;
   TRY(categorical_bwd_gated(s, p->yprob, p->dy, gate, w * inv_gb, p->dlogits, B, K, prior));
   if (c.prior_mode == 2)   // learned p(y): this rank's share of the gradient of w * KL_y_modified
     TRY(prior_logits_bwd(s, p->yprob, prior, gate, w * inv_gb, w * share, c.free_nats_proportion,
@@ -860,12 +601,116 @@ int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
     TRY(dense_backward(p, s, d, in, d.n_in, B, 1, true, dh, scratch, d_in, false, GB));
     if (i > 0) { float* t = dh; dh = dh_alt; dh_alt = t; }
   }
-
-  // ---------------- batch-norm moving averages (K passes update in pass order) --------
   // (the batch-norm moving averages were updated by the layers' backward statistics launches)
-#undef GEMM
-#undef TRY
   return 0;
+}
+
+int GmStep::step() {
+  const scvae_model_config& c = p->cfg;
+  p->drop_seed = a->dropout_seed;
+  TRY(forward_qy());
+  TRY(forward_qz());
+  TRY(latent());
+
+  // ---------------- decoder p(x|z_k), all k (gm:3094-3221) ----------------
+  const int E = c.decoder_extra;
+  dec_in = p->z;
+  if (E > 0) {
+    TRY(concat_extra(s, p->z, L, a->decoder_extra, E, (size_t)R, (size_t)B, p->zcat));
+    dec_in = p->zcat;
+  }
+  const float* dch = dec_in;
+  int ld = L + E;
+  if (tile) {
+    TRY(tile_decoder_forward(tc, p->xdec, dec_in, L, R, K, SB));
+    dch = p->xdec.back().h; ld = p->xdec.back().n_out;
+  } else {
+    for (auto& d : p->xdec) {
+      TRY(dense_forward(p, s, d, dch, ld, R, K, true, training));
+      dch = d.h; ld = d.n_out;
+    }
+  }
+  // the head stage (plan.hip): fused heads + likelihood (+ backward) unless the evaluate-time
+  // statistics are requested; one forward pass over the K stacked passes
+  HeadPath hd;
+  TRY(head_path(p, a, s, training, 1, dch, ld, R, B, &hd));
+  const int KM = hd.KM, FC = F * (KM + 1);
+  bool ll_done = false;
+  if (a->p_x_mean) {
+    TRY(head_px_begin(p, a, s, hd, &ll_done));
+    for (int k = 0; k < K; ++k) {
+      HeadPtrs pk;
+      for (int j = 0; j < 3; ++j)
+        pk.p[j] = p->pre[j] ? p->pre[j] + (size_t)k * SB * F : nullptr;
+      if (KM > 0)
+        TRY(px_statistics_cat(s, c.likelihood, pk, F, p->pre_k + (size_t)k * SB * FC, KM, S, B, F,
+                              p->yprob + k, K, k > 0 ? 1 : 0, a->p_x_mean, p->mov, p->vom));
+      else
+        TRY(px_statistics(s, c.likelihood, pk, F, S, B, F, p->yprob + k, K, k > 0 ? 1 : 0,
+                          a->p_x_mean, p->mov, p->vom));
+    }
+    TRY(head_px_finish(p, a, s, hd));
+  }
+
+  // ---------------- loss (gm:3223-3410) ----------------
+  float* sums = p->kl_cell + B;     // 3 floats (+ gate at [8])
+  gate = sums + 8;
+  const float p_y_entropy = logf((float)K);
+  const float thr = c.free_nats_proportion * p_y_entropy;
+  const int use_free_nats = c.free_nats_proportion != 0.f;
+  if (!training) {
+    if (!ll_done) TRY(head_loglik_forward(p, a, s, hd));
+    TRY(gmvae_elbo(s, p->ll, p->klz, p->yprob, p->kl_y_cell, K, S, B, inv_gb, sums, nullptr));
+    TRY(gmvae_elbo_finish(s, sums, w, thr, use_free_nats, 1.f, a->scalars, gate, prior, K,
+                          c.free_nats_proportion));
+    if (a->log_p_x_given_z) TRY(copy(s, p->ll, a->log_p_x_given_z, (size_t)R));
+    return 0;
+  }
+  // d(-ELBO_w)/d log p(t|z_k)[k,s,b] = -y[b,k]/(S*GB): known before the likelihood pass
+  TRY(gmvae_elbo_bwd(s, p->klz, p->klz, p->yprob, gate, K, S, B, w, inv_gb, p->gw, p->gklz,
+                     p->dy));  // (fills gw, gklz; dy is recomputed below with ll)
+  float* dcur = p->dbuf[0];
+  float* dalt = p->dbuf[1];
+  TRY(head_train(p, a, s, hd, dcur));
+  TRY(gmvae_elbo(s, p->ll, p->klz, p->yprob, p->kl_y_cell, K, S, B, inv_gb, sums, nullptr));
+  if (p->sync) {
+    // the free-nats gate depends on the global kl_divergence_y
+    if (p->sync(p->sync_user, sums, 3, 0, B)) {
+      set_error("ELBO sync hook failed");
+      return -2;
+    }
+    share = (float)a->cells / (float)GB;
+  }
+  TRY(gmvae_elbo_finish(s, sums, w, thr, use_free_nats, share, a->scalars, gate, prior, K,
+                        c.free_nats_proportion));
+  TRY(gmvae_elbo_bwd(s, p->ll, p->klz, p->yprob, gate, K, S, B, w, inv_gb, p->gw, p->gklz, p->dy));
+  if (a->log_p_x_given_z) TRY(copy(s, p->ll, a->log_p_x_given_z, (size_t)R));
+
+  // ---------------- backward ----------------
+  TRY(head_backward(p, s, hd, dcur, dalt));
+  // the next minibatch and its noise (scvae_step_args.side) under the rest of the backward pass
+  TRY(plan_side_fork(p, s, 1));
+  TRY(backward_decoder(dcur, dalt));
+  TRY(backward_latent());
+  TRY(backward_qz());
+  return backward_qy();
+}
+
+int gmvae_step(scvae_plan* p, const scvae_step_args* a, hipStream_t s) {
+  const scvae_model_config& c = p->cfg;
+  GmStep g;
+  g.p = p; g.a = a; g.s = s;
+  g.K = c.n_clusters; g.B = (int)a->cells; g.S = a->n_iw * a->n_mc;
+  g.KB = g.K * g.B; g.SB = g.S * g.B; g.R = g.K * g.SB;
+  g.F = c.feature_size; g.L = c.latent_size; g.Ls = p->qscale.n_out;
+  g.fullcov = (c.latent_mode & 8) != 0;
+  g.training = a->training != 0;
+  g.tile = gm_tile_chain_ok(p, g.B, g.S, g.training);
+  g.GB = a->global_cells > 0 ? a->global_cells : a->cells;
+  g.w = a->warm_up_weight * c.kl_weight;
+  g.inv_gb = 1.f / (float)g.GB;
+  g.tc.p = p; g.tc.s = s;
+  return g.step();
 }
 
 }  // namespace scvae
