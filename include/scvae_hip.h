@@ -691,6 +691,29 @@ int scvae_philox_normal_blocks(float* out, int64_t blocks, int64_t block_rows, i
 int scvae_bn_merge(const float* gathered, const int64_t* counts, int64_t ranks, int64_t n,
                    float* out, void* stream);
 
+/* ---- k-means over latent values (scvae/analyses/prediction.py:33-131: the clustering behind
+ *      `-P k-means`), exact Lloyd passes.  x [N, L] fp32 with row pitch ldx, centres [K, L] fp32,
+ *      labels int32.  1 <= K <= 256, 1 <= L <= 256, K L <= 8192, K <= N < 2^31; anything else
+ *      returns -1 and scvae_last_error() names the limit.  Every sum has one fixed order (no
+ *      floating-point atomics): the same inputs give the same bits on every run. ---- */
+/* bytes of the 8-byte aligned workspace of scvae_kmeans_assign / _update for these sizes */
+int64_t scvae_kmeans_workspace_bytes(int64_t N, int64_t L, int64_t K);
+/* labels[i] = argmin_k sum_l (x_il - c_kl)^2 (direct form, fp32; the lowest k on equal
+ * distances), min_d2[i] (optional) that distance, *inertia (device fp64) their sum */
+int scvae_kmeans_assign(const float* x, int64_t ldx, int64_t N, int64_t L, const float* centres,
+                        int64_t K, int32_t* labels, float* min_d2, double* inertia,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+/* new_centres[k] = mean of the rows labelled k (fp64 sums over fixed row ranges, rounded to fp32
+ * once); a cluster without rows keeps centres[k] -- it is not relocated.  counts[K] (device
+ * int32), *shift (device fp64) = sum_k |new_centres[k] - centres[k]|^2.  new_centres may be
+ * centres.  A label outside [0, K) counts for no cluster. */
+int scvae_kmeans_update(const float* x, int64_t ldx, int64_t N, int64_t L, const int32_t* labels,
+                        const float* centres, int64_t K, float* new_centres, int32_t* counts,
+                        double* shift, void* workspace, int64_t workspace_bytes, void* stream);
+/* min_d2[i] = min(min_d2[i], |x_i - x_j|^2): the pass k-means++ makes for every centre it picks */
+int scvae_kmeans_min_d2_update(const float* x, int64_t ldx, int64_t N, int64_t L, int64_t j,
+                               float* min_d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,6 +303,15 @@ SIGNATURES = {
         c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scvae_bn_merge": (c_int32, [
         c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "scvae_kmeans_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "scvae_kmeans_assign": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+        c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_kmeans_update": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_kmeans_min_d2_update": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

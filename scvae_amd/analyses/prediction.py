@@ -3,7 +3,8 @@
 of a training set ("k-means"), or take the clusters a GMVAE assigned itself
 ("model"), and name every cluster after the most frequent label of its cells.
 Host-side NumPy / scikit-learn work on the ``[cells, latent]`` outputs of
-``model.evaluate``; nothing here runs on the GPU.
+``model.evaluate``; nothing here runs on the GPU unless ``on_device`` is set,
+which hands the k-means to ``analyses/kmeans.py``.
 """
 from time import time
 
@@ -81,7 +82,20 @@ def _dense(values):
 
 
 @_register("k-means")
-def _predict_using_kmeans(training_set, evaluation_set, number_of_clusters):
+def _predict_using_kmeans(training_set, evaluation_set, number_of_clusters,
+                          on_device=False):
+    if on_device:
+        from scvae_amd.analyses.kmeans import DeviceKMeans, limit_reason
+        training_values = _dense(training_set.values)
+        reason = limit_reason(
+            training_values.shape[0],
+            training_values.shape[1] if training_values.ndim == 2 else 0,
+            number_of_clusters)
+        if reason is None:
+            model = DeviceKMeans(number_of_clusters).fit(training_values)
+            return model.predict(_dense(evaluation_set.values)), None, None
+        print("k-means on the device not used: {}; using scikit-learn."
+              .format(reason))
     from sklearn.cluster import KMeans, MiniBatchKMeans
     if (training_set.number_of_examples
             <= MAXIMUM_SAMPLE_SIZE_FOR_NORMAL_KMEANS):
@@ -95,7 +109,8 @@ def _predict_using_kmeans(training_set, evaluation_set, number_of_clusters):
 
 
 @_register("model")
-def _predict_using_model(training_set, evaluation_set, number_of_clusters):
+def _predict_using_model(training_set, evaluation_set, number_of_clusters,
+                         on_device=False):
     # what the model attached in evaluate() (gm:2744-2781)
     return (evaluation_set.predicted_cluster_ids,
             evaluation_set.predicted_labels,
@@ -103,7 +118,7 @@ def _predict_using_model(training_set, evaluation_set, number_of_clusters):
 
 
 def predict_labels(training_set, evaluation_set, specifications=None,
-                   method=None, number_of_clusters=None):
+                   method=None, number_of_clusters=None, on_device=False):
     if specifications is None:
         if method is None:
             method = defaults["evaluation"]["prediction_method"]
@@ -116,7 +131,8 @@ def predict_labels(training_set, evaluation_set, specifications=None,
     start = time()
     cluster_ids, predicted_labels, predicted_superset_labels = predict(
         training_set=training_set, evaluation_set=evaluation_set,
-        number_of_clusters=specifications.number_of_clusters)
+        number_of_clusters=specifications.number_of_clusters,
+        on_device=on_device)
     if (cluster_ids is not None and predicted_labels is None
             and evaluation_set.has_labels):
         to_id = evaluation_set.class_name_to_class_id

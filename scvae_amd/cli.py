@@ -208,8 +208,13 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              splitting_fraction=None, minibatch_size=None, run_id=None,
              models_directory=None, evaluation_set_kind=None,
              sample_size=None, model_versions=None, prediction_method=None,
-             prediction_training_set_kind=None, **keyword_arguments):
-    """Evaluate model on data set (``cli.py:267-566``)."""
+             prediction_training_set_kind=None, prediction_on_device=False,
+             **keyword_arguments):
+    """Evaluate model on data set (``cli.py:267-566``).
+
+    ``prediction_on_device`` (not in the reference): run the k-means of the
+    prediction on the GPU (``analyses/kmeans.py``: exact Lloyd for every
+    number of cells) instead of scikit-learn on the host."""
     if prediction_method is None:
         prediction_method = defaults["evaluation"]["prediction_method"]
     if prediction_training_set_kind is None:
@@ -333,13 +338,14 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
         if prediction_specifications is not None:   # cli.py:509-543
             _predict(model, results[model_version], prediction_training_set,
                      prediction_specifications, minibatch_size, run_id,
-                     use_best_model, use_early_stopping_model, model_version)
+                     use_best_model, use_early_stopping_model, model_version,
+                     on_device=bool(prediction_on_device))
     return results
 
 
 def _predict(model, version_results, prediction_training_set, specifications,
              minibatch_size, run_id, use_best_model, use_early_stopping_model,
-             model_version):
+             model_version, on_device=False):
     """Cluster the latent representation and attach the predicted labels to
     every version of the evaluation set (``cli.py:509-543``)."""
     from scvae_amd.analyses.prediction import (
@@ -357,7 +363,8 @@ def _predict(model, version_results, prediction_training_set, specifications,
     print()
     cluster_ids, predicted_labels, predicted_superset_labels = predict_labels(
         training_set=latent_training_sets["z"],
-        evaluation_set=latent_sets["z"], specifications=specifications)
+        evaluation_set=latent_sets["z"], specifications=specifications,
+        on_device=on_device)
     for version in [transformed, reconstructed] + list(latent_sets.values()):
         version.update_predictions(
             prediction_specifications=specifications,
@@ -601,6 +608,13 @@ def main(arguments=None):
             defaults["evaluation"]["prediction_training_set_kind"]),
         help="kind of subset to fit the prediction method on: training, "
              "validation, test, or full")
+    parser_evaluate.add_argument(
+        "--prediction-on-device", action="store_true", default=False,
+        help="(this build) run the k-means of -P k-means on the GPU: exact "
+             "Lloyd iterations for every number of cells (scikit-learn's "
+             "mini-batch k-means takes over above 10 000 cells otherwise); at "
+             "most 256 clusters, 256 latent values and 8192 centre values, "
+             "else scikit-learn as without the switch")
     parser_evaluate.add_argument(
         "--model-versions", metavar="VERSION", nargs="+",
         default=_parse_default(defaults["evaluation"]["model_versions"]),
