@@ -714,6 +714,26 @@ int scvae_kmeans_update(const float* x, int64_t ldx, int64_t N, int64_t L, const
 int scvae_kmeans_min_d2_update(const float* x, int64_t ldx, int64_t N, int64_t L, int64_t j,
                                float* min_d2, void* stream);
 
+/* ---- silhouette values of a clustering of latent values
+ *      (scvae/analyses/metrics/clustering.py:120-142: the "silhouette score" of a label
+ *      prediction; scikit-learn's silhouette_samples, Euclidean), exact over every pair of rows.
+ *      x [N, L] fp32 with row pitch ldx, its rows grouped by cluster: cluster k holds rows
+ *      offsets[k] .. offsets[k + 1] - 1 (offsets: DEVICE int64 [K + 1], strictly increasing,
+ *      offsets[0] = 0, offsets[K] = N).  1 <= L <= 256, 3 <= N < 2^31, 2 <= K <= N - 1; anything
+ *      else returns -1 and scvae_last_error() names the limit.  Distances in the direct form
+ *      sqrt(sum_l (x_il - x_jl)^2) in fp32; every sum has one fixed order (no floating-point
+ *      atomics): the same inputs give the same bits on every run. ---- */
+/* bytes of the 8-byte aligned workspace of scvae_silhouette_samples for these sizes */
+int64_t scvae_silhouette_workspace_bytes(int64_t N, int64_t L, int64_t K);
+/* a[i] = mean distance to the other rows of the own cluster (0 in a cluster of one row),
+ * b[i] = the lowest mean distance to the rows of another cluster, s[i] = (b - a) / max(a, b)
+ * (0 in a cluster of one row and when max(a, b) = 0): fp32 [N] each, in the grouped row order,
+ * each optional (NULL).  *score (device fp64) = the mean of s. */
+int scvae_silhouette_samples(const float* x, int64_t ldx, int64_t N, int64_t L,
+                             const int64_t* offsets, int64_t K, float* a, float* b, float* s,
+                             double* score, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

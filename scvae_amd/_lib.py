@@ -312,6 +312,10 @@ SIGNATURES = {
         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "scvae_kmeans_min_d2_update": (c_int32, [
         c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "scvae_silhouette_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "scvae_silhouette_samples": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@ of a training set ("k-means"), or take the clusters a GMVAE assigned itself
 ("model"), and name every cluster after the most frequent label of its cells.
 Host-side NumPy / scikit-learn work on the ``[cells, latent]`` outputs of
 ``model.evaluate``; nothing here runs on the GPU unless ``on_device`` is set,
-which hands the k-means to ``analyses/kmeans.py``.
+which hands the k-means to ``analyses/kmeans.py``, or the silhouette score is
+asked for (``silhouette_metric``, ``analyses/silhouette.py``).
 """
 from time import time
 
@@ -14,6 +15,7 @@ from scvae_amd.defaults import defaults
 from scvae_amd.utilities import format_duration, normalise_string
 
 MAXIMUM_SAMPLE_SIZE_FOR_NORMAL_KMEANS = 10000
+MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE = 20000
 PREDICTION_METHODS = {}
 
 
@@ -169,3 +171,37 @@ def clustering_metrics(labels, predicted_cluster_ids, predicted_labels=None,
         metrics["accuracy"] = float(numpy.mean(
             numpy.asarray(predicted_labels)[keep] == labels[keep]))
     return metrics
+
+
+def silhouette_metric(values, predicted_ids):
+    """The silhouette score of ``predicted_ids`` over ``values`` ([cells,
+    latent]; ``analyses/metrics/clustering.py:120-142``): ``nan`` for fewer
+    than 2 or more than cells - 1 distinct ids, else the exact score over
+    every cell on the GPU (``analyses/silhouette.py``).  Sizes the kernel does
+    not take get one line saying so and what the reference computes:
+    scikit-learn on the host, sampled down to 20 000 cells above 20 000.
+
+    The reference scores the clustering in count space (cells x genes); this
+    scores it in the latent space the clustering was made in."""
+    from scvae_amd.analyses import silhouette
+    values = _dense(values)
+    predicted_ids = numpy.asarray(predicted_ids).reshape(-1)
+    number_of_examples = values.shape[0]
+    number_of_predicted_classes = numpy.unique(predicted_ids).shape[0]
+    if (number_of_predicted_classes < 2
+            or number_of_predicted_classes > number_of_examples - 1):
+        return float("nan")
+    reason = silhouette.limit_reason(
+        number_of_examples, values.shape[1] if values.ndim == 2 else 0,
+        number_of_predicted_classes)
+    if reason is None:
+        return float(silhouette.silhouette_score(values, predicted_ids))
+    print("silhouette score on the device not used: {}.".format(reason))
+    import sklearn.metrics
+    sample_size = None
+    if (number_of_examples
+            > MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE):
+        sample_size = (
+            MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE)
+    return float(sklearn.metrics.silhouette_score(
+        X=values, labels=predicted_ids, sample_size=sample_size))

@@ -209,12 +209,20 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              models_directory=None, evaluation_set_kind=None,
              sample_size=None, model_versions=None, prediction_method=None,
              prediction_training_set_kind=None, prediction_on_device=False,
-             **keyword_arguments):
+             silhouette_score=False, **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
 
     ``prediction_on_device`` (not in the reference): run the k-means of the
     prediction on the GPU (``analyses/kmeans.py``: exact Lloyd for every
-    number of cells) instead of scikit-learn on the host."""
+    number of cells) instead of scikit-learn on the host.
+
+    ``silhouette_score``: also print the silhouette score of the predicted
+    clusters (and of the predicted labels), the third clustering metric of
+    the reference (``analyses/metrics/clustering.py:120-142``), computed on
+    the GPU (``analyses/silhouette.py``).  The reference scores the
+    clustering in count space (cells x genes) and samples it down to 20 000
+    cells; this scores it in the latent space the clustering was made in,
+    exactly, over every cell."""
     if prediction_method is None:
         prediction_method = defaults["evaluation"]["prediction_method"]
     if prediction_training_set_kind is None:
@@ -339,17 +347,21 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             _predict(model, results[model_version], prediction_training_set,
                      prediction_specifications, minibatch_size, run_id,
                      use_best_model, use_early_stopping_model, model_version,
-                     on_device=bool(prediction_on_device))
+                     on_device=bool(prediction_on_device),
+                     silhouette_score=bool(silhouette_score))
     return results
 
 
 def _predict(model, version_results, prediction_training_set, specifications,
              minibatch_size, run_id, use_best_model, use_early_stopping_model,
-             model_version, on_device=False):
+             model_version, on_device=False, silhouette_score=False):
     """Cluster the latent representation and attach the predicted labels to
-    every version of the evaluation set (``cli.py:509-543``)."""
+    every version of the evaluation set (``cli.py:509-543``).  With
+    ``silhouette_score`` the silhouette scores of the predicted clusters and
+    labels over the latent values of the evaluation set follow the metrics
+    (a set without labels gets the header and these lines alone)."""
     from scvae_amd.analyses.prediction import (
-        clustering_metrics, predict_labels)
+        clustering_metrics, predict_labels, silhouette_metric)
     print(subtitle("Prediction ({})".format(model_version.replace("_", " "))))
     evaluation_results = (version_results[0]
                           if isinstance(version_results, tuple)
@@ -378,6 +390,16 @@ def _predict(model, version_results, prediction_training_set, specifications,
             transformed.kind, specifications.name))
         for name, value in metrics.items():
             print("    {}: {:.4f}".format(name, value))
+    if silhouette_score and cluster_ids is not None:
+        if not transformed.has_labels:
+            print("Clustering of the {} set ({}):".format(
+                transformed.kind, specifications.name))
+        latent_values = latent_sets["z"].values
+        print("    silhouette score (clusters): {:.4f}".format(
+            silhouette_metric(latent_values, cluster_ids)))
+        if predicted_labels is not None:
+            print("    silhouette score (labels): {:.4f}".format(
+                silhouette_metric(latent_values, predicted_labels)))
     print()
 
 
@@ -615,6 +637,13 @@ def main(arguments=None):
              "mini-batch k-means takes over above 10 000 cells otherwise); at "
              "most 256 clusters, 256 latent values and 8192 centre values, "
              "else scikit-learn as without the switch")
+    parser_evaluate.add_argument(
+        "--silhouette-score", action="store_true", default=False,
+        help="(this build) with -P, also print the silhouette score of the "
+             "predicted clusters and labels: exact over every cell, on the "
+             "GPU, in the latent space (the reference scores a sample of "
+             "20 000 cells in count space); at most 256 latent values, else "
+             "scikit-learn on the host")
     parser_evaluate.add_argument(
         "--model-versions", metavar="VERSION", nargs="+",
         default=_parse_default(defaults["evaluation"]["model_versions"]),
