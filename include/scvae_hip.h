@@ -734,6 +734,36 @@ int scvae_silhouette_samples(const float* x, int64_t ldx, int64_t N, int64_t L,
                              double* score, void* workspace, int64_t workspace_bytes,
                              void* stream);
 
+/* ---- silhouette values of a clustering in COUNT space (the space the reference scores in,
+ *      clustering.py:120-142), exact pairwise distances between count rows on the matrix cores.
+ *      x [N, F] uint16 counts in the layout of scvae_csr_densify_u16: row pitch ldx a multiple
+ *      of 8 and at least F rounded up to 64, pad columns zero, 16-byte aligned base.
+ *      1 <= F <= 65 536, 3 <= N <= 2^20, 2 <= K <= N - 1; anything else returns -1 and
+ *      scvae_last_error() names the limit.  d2(i, j) = sum_g (x_ig - x_jg)^2 is computed exactly
+ *      in integers (int8 byte products with int32 accumulators, put together in int64);
+ *      d(i, j) = (float)sqrt((double)d2), within (2^-24 + 2^-51) relative, 0 exactly for equal
+ *      rows and for no others, d(i, j) = d(j, i) bit for bit.  No floating-point atomics: the
+ *      same inputs give the same bits on every run.  Symmetry is not exploited. ---- */
+/* bytes of the 8-byte aligned workspace scvae_count_silhouette_samples_u16 is best given: 8 N
+ * (a row moment, int64) + 4 N rounded up to 8 (s of every row) + a strip of R rows of distances,
+ * 4 R P bytes with P = N rounded up to 16 and R the whole tiles of 128 rows that fit 256 MiB (at
+ * least 128; N where all rows fit).  The entry takes any workspace that holds a strip of
+ * min(N, 128) rows and chooses R from what it is given. */
+int64_t scvae_count_silhouette_workspace_bytes(int64_t N, int64_t F, int64_t K);
+/* d[r][j] = d(i0 + r, j) for r < rows, j < N: fp32 with row pitch ldd >= N, one strip of the
+ * distance matrix (0 <= i0, 1 <= rows, i0 + rows <= N).  workspace: 8 N bytes, 8-byte aligned. */
+int scvae_count_distances_u16(const uint16_t* x, int64_t ldx, int64_t N, int64_t F, int64_t i0,
+                              int64_t rows, float* d, int64_t ldd, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+/* The rows grouped by cluster: cluster k holds rows offsets[k] .. offsets[k + 1] - 1 (offsets:
+ * DEVICE int64 [K + 1], strictly increasing, offsets[0] = 0, offsets[K] = N).  a, b, s as for
+ * scvae_silhouette_samples: fp32 [N] in the grouped row order, each optional (NULL); *score
+ * (device fp64) = the mean of s.  Sums of distances are taken in fp64 in one fixed order. */
+int scvae_count_silhouette_samples_u16(const uint16_t* x, int64_t ldx, int64_t N, int64_t F,
+                                       const int64_t* offsets, int64_t K, float* a, float* b,
+                                       float* s, double* score, void* workspace,
+                                       int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -316,6 +316,14 @@ SIGNATURES = {
     "scvae_silhouette_samples": (c_int32, [
         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_count_silhouette_workspace_bytes": (c_int64, [c_int64, c_int64,
+                                                         c_int64]),
+    "scvae_count_distances_u16": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+        c_int64, c_void_p, c_int64, c_void_p]),
+    "scvae_count_silhouette_samples_u16": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

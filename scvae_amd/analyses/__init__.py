@@ -7,3 +7,5 @@ from scvae_amd.analyses.prediction import (  # noqa: F401
     map_cluster_ids_to_label_ids)
 from scvae_amd.analyses.silhouette import (  # noqa: F401
     silhouette_samples, silhouette_score)
+from scvae_amd.analyses.count_silhouette import (  # noqa: F401
+    count_silhouette_samples, count_silhouette_score)

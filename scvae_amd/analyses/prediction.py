@@ -5,7 +5,9 @@ of a training set ("k-means"), or take the clusters a GMVAE assigned itself
 Host-side NumPy / scikit-learn work on the ``[cells, latent]`` outputs of
 ``model.evaluate``; nothing here runs on the GPU unless ``on_device`` is set,
 which hands the k-means to ``analyses/kmeans.py``, or the silhouette score is
-asked for (``silhouette_metric``, ``analyses/silhouette.py``).
+asked for (``silhouette_metric``, ``analyses/silhouette.py``, over the latent
+values; ``count_silhouette_metric``, ``analyses/count_silhouette.py``, over
+the counts).
 """
 from time import time
 
@@ -205,3 +207,45 @@ def silhouette_metric(values, predicted_ids):
             MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE)
     return float(sklearn.metrics.silhouette_score(
         X=values, labels=predicted_ids, sample_size=sample_size))
+
+
+def count_silhouette_metric(values, predicted_ids, random_state=None):
+    """The silhouette score of ``predicted_ids`` over ``values`` in count
+    space ([cells, genes], sparse or dense), as the reference takes it
+    (``analyses/metrics/clustering.py:120-142``): ``nan`` for fewer than 2 or
+    more than cells - 1 distinct ids; above 20 000 cells a sample of 20 000
+    (``sklearn.metrics.silhouette_score(sample_size=20000)``: the first 20 000
+    of ``RandomState(random_state).permutation(cells)``).  Integer counts
+    below 65 536 are scored on the GPU with exact distances
+    (``analyses/count_silhouette.py``); anything else gets one line saying
+    why and what the reference computes: scikit-learn on the host with the
+    same ``sample_size``."""
+    from scvae_amd.analyses import count_silhouette
+    predicted_ids = numpy.asarray(predicted_ids).reshape(-1)
+    number_of_examples = values.shape[0]
+    number_of_predicted_classes = numpy.unique(predicted_ids).shape[0]
+    if (number_of_predicted_classes < 2
+            or number_of_predicted_classes > number_of_examples - 1):
+        return float("nan")
+    sample_size = None
+    if (number_of_examples
+            > MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE):
+        sample_size = (
+            MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE)
+    # the sizes of what the device would score: the sample (which clusters it
+    # keeps is known once it is drawn; a sample of one cluster is an error
+    # there as it is in scikit-learn)
+    number_scored = sample_size or number_of_examples
+    reason = count_silhouette.limit_reason(
+        number_scored, values.shape[1] if len(values.shape) == 2 else 0,
+        min(number_of_predicted_classes, number_scored - 1), values)
+    if reason is None:
+        return float(count_silhouette.count_silhouette_score(
+            values, predicted_ids, sample_size=sample_size,
+            random_state=random_state))
+    print("count-space silhouette score on the device not used: {}.".format(
+        reason))
+    import sklearn.metrics
+    return float(sklearn.metrics.silhouette_score(
+        X=values, labels=predicted_ids, sample_size=sample_size,
+        random_state=random_state))

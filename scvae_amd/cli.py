@@ -209,7 +209,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              models_directory=None, evaluation_set_kind=None,
              sample_size=None, model_versions=None, prediction_method=None,
              prediction_training_set_kind=None, prediction_on_device=False,
-             silhouette_score=False, **keyword_arguments):
+             silhouette_score=False, silhouette_space="latent",
+             **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
 
     ``prediction_on_device`` (not in the reference): run the k-means of the
@@ -222,7 +223,17 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     the GPU (``analyses/silhouette.py``).  The reference scores the
     clustering in count space (cells x genes) and samples it down to 20 000
     cells; this scores it in the latent space the clustering was made in,
-    exactly, over every cell."""
+    exactly, over every cell.
+
+    ``silhouette_space`` (read only with ``silhouette_score``): ``"latent"``,
+    the above, or ``"counts"``, the reference's own quantity: the score over
+    the values of the evaluation set in count space, 20 000 cells sampled
+    above 20 000, with exact distances on the GPU
+    (``analyses/count_silhouette.py``)."""
+    silhouette_space = normalise_string(str(silhouette_space))
+    if silhouette_score and silhouette_space not in ("latent", "counts"):
+        raise ValueError("Silhouette space `{}` not found.".format(
+            silhouette_space))
     if prediction_method is None:
         prediction_method = defaults["evaluation"]["prediction_method"]
     if prediction_training_set_kind is None:
@@ -348,20 +359,30 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
                      prediction_specifications, minibatch_size, run_id,
                      use_best_model, use_early_stopping_model, model_version,
                      on_device=bool(prediction_on_device),
-                     silhouette_score=bool(silhouette_score))
+                     silhouette_score=bool(silhouette_score),
+                     silhouette_space=silhouette_space)
     return results
 
 
 def _predict(model, version_results, prediction_training_set, specifications,
              minibatch_size, run_id, use_best_model, use_early_stopping_model,
-             model_version, on_device=False, silhouette_score=False):
+             model_version, on_device=False, silhouette_score=False,
+             silhouette_space="latent"):
     """Cluster the latent representation and attach the predicted labels to
     every version of the evaluation set (``cli.py:509-543``).  With
     ``silhouette_score`` the silhouette scores of the predicted clusters and
     labels over the latent values of the evaluation set follow the metrics
-    (a set without labels gets the header and these lines alone)."""
+    (a set without labels gets the header and these lines alone).  With
+    ``silhouette_space="counts"`` they are taken over the values of the
+    evaluation set in count space instead -- the transformed evaluation set,
+    which is what the reference's metric receives (``cli.py:548-550`` hands it
+    to ``analyse_results``, ``analyses.py:894-895`` to
+    ``compute_clustering_metrics``, ``clustering.py:73-82`` takes its
+    ``values``)."""
     from scvae_amd.analyses.prediction import (
-        clustering_metrics, predict_labels, silhouette_metric)
+        MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE,
+        clustering_metrics, count_silhouette_metric, predict_labels,
+        silhouette_metric)
     print(subtitle("Prediction ({})".format(model_version.replace("_", " "))))
     evaluation_results = (version_results[0]
                           if isinstance(version_results, tuple)
@@ -394,12 +415,26 @@ def _predict(model, version_results, prediction_training_set, specifications,
         if not transformed.has_labels:
             print("Clustering of the {} set ({}):".format(
                 transformed.kind, specifications.name))
-        latent_values = latent_sets["z"].values
-        print("    silhouette score (clusters): {:.4f}".format(
-            silhouette_metric(latent_values, cluster_ids)))
-        if predicted_labels is not None:
-            print("    silhouette score (labels): {:.4f}".format(
-                silhouette_metric(latent_values, predicted_labels)))
+        if silhouette_space == "counts":
+            count_values = transformed.values
+            cells = count_values.shape[0]
+            limit = MAXIMUM_NUMBER_OF_EXAMPLES_BEFORE_SAMPLING_SILHOUETTE_SCORE
+            if cells > limit:
+                print("    (count space: {} of {} cells sampled)".format(
+                    limit, cells))
+            print("    silhouette score (clusters; count space): {:.4f}"
+                  .format(count_silhouette_metric(count_values, cluster_ids)))
+            if predicted_labels is not None:
+                print("    silhouette score (labels; count space): {:.4f}"
+                      .format(count_silhouette_metric(
+                          count_values, predicted_labels)))
+        else:
+            latent_values = latent_sets["z"].values
+            print("    silhouette score (clusters): {:.4f}".format(
+                silhouette_metric(latent_values, cluster_ids)))
+            if predicted_labels is not None:
+                print("    silhouette score (labels): {:.4f}".format(
+                    silhouette_metric(latent_values, predicted_labels)))
     print()
 
 
@@ -644,6 +679,13 @@ def main(arguments=None):
              "GPU, in the latent space (the reference scores a sample of "
              "20 000 cells in count space); at most 256 latent values, else "
              "scikit-learn on the host")
+    parser_evaluate.add_argument(
+        "--silhouette-space", choices=["latent", "counts"], default="latent",
+        help="(this build) with --silhouette-score: latent, the above, or "
+             "counts, the reference's own quantity: the score over the "
+             "counts of the evaluation set, 20 000 cells sampled above "
+             "20 000, with exact distances on the GPU (integer counts below "
+             "65 536, at most 65 536 genes, else scikit-learn on the host)")
     parser_evaluate.add_argument(
         "--model-versions", metavar="VERSION", nargs="+",
         default=_parse_default(defaults["evaluation"]["model_versions"]),
