@@ -764,6 +764,41 @@ int scvae_count_silhouette_samples_u16(const uint16_t* x, int64_t ldx, int64_t N
                                        float* s, double* score, void* workspace,
                                        int64_t workspace_bytes, void* stream);
 
+/* ---- summary statistics of the evaluation set and of its reconstruction
+ *      (scvae/analyses/metrics/summary.py:27-57: mean, standard deviation with ddof 1, minimum,
+ *      maximum and, through data/sparse.py:65-89, the count of elements >= tolerance; the
+ *      metrics table of analyses/analyses.py:873-895 with the comparison arrays of
+ *      analyses.py:796-802), accumulated over blocks of rows in one streaming pass each.
+ *      Four element streams: 0 orig x, 1 recon x~, 2 differences |x~ - x|, 3 log-ratios
+ *      |log1p x~ - log1p x|; the elements of 2 and 3 are formed in fp64 from the fp32 inputs (the
+ *      reference rounds them to fp32).  Sums are fp64, the variance by two-pass partials of 16
+ *      elements joined pairwise with Chan's formula (no sum of x^2 - mean^2 cancellation), n and
+ *      the counts int64, all indices int64.  A NaN element makes mean, standard deviation,
+ *      minimum and maximum of its stream NaN and is not counted as >= tolerance.  No
+ *      floating-point atomics: the same sequence of calls on the same data gives the same bits
+ *      on every run.  Bad arguments return -1 and scvae_last_error() names them; nothing is
+ *      launched then. ---- */
+/* bytes of the 8-byte aligned workspace the three entries below share: the state the calls add
+ * to, and the workgroups' partial results of one call */
+int64_t scvae_summary_workspace_bytes(void);
+/* empties the state (n = 0 in every stream) */
+int scvae_summary_reset(void* workspace, int64_t workspace_bytes, void* stream);
+/* adds rows x F elements to the state: recon [rows, F] fp32 with row pitch ldr and orig
+ * [rows, F] fp32 with row pitch ldo, either one optional (NULL) but not both; rows >= 1,
+ * 1 <= F < 2^31 - 8192 (rows x pitch is not limited: element offsets are int64),
+ * pitches >= F, 4-byte aligned bases (16-byte loads are used wherever a row's alignment allows;
+ * columns F .. pitch - 1 are never read).  Stream 0 takes orig, stream 1 recon; comparisons != 0
+ * (both inputs needed) adds streams 2 and 3.  tolerance: an element e of stream 0 or 1 is counted
+ * when (double)e >= tolerance. */
+int scvae_summary_accumulate(const float* recon, int64_t ldr, const float* orig, int64_t ldo,
+                             int64_t rows, int64_t F, double tolerance, int32_t comparisons,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+/* stats [4][4] (device fp64) = mean, standard deviation (ddof 1; NaN for n < 2), minimum, maximum
+ * of each stream, NaN for a stream without elements; counts [4][2] (device int64) = n and the
+ * number of elements >= tolerance (0 for streams 2 and 3).  The state is left as it is. */
+int scvae_summary_finish(const void* workspace, int64_t workspace_bytes, double* stats,
+                         int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,8 +7,8 @@ when it has not been built (``python __graft_entry__.py`` or
 
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int32, c_int64,
-                    c_uint64, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32,
+                    c_int64, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 #: (SCVAE_HIP_LIBRARY: an A/B build of the same library, tools/ab_variants.sh)
@@ -324,6 +324,13 @@ SIGNATURES = {
     "scvae_count_silhouette_samples_u16": (c_int32, [
         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_summary_workspace_bytes": (c_int64, []),
+    "scvae_summary_reset": (c_int32, [c_void_p, c_int64, c_void_p]),
+    "scvae_summary_accumulate": (c_int32, [
+        c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_double,
+        c_int32, c_void_p, c_int64, c_void_p]),
+    "scvae_summary_finish": (c_int32, [
+        c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

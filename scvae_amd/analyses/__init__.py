@@ -1,7 +1,10 @@
 """The part of ``scvae.analyses`` that ``scvae evaluate`` needs to report
-cluster quality: label prediction from the latent representation
-(``scvae/analyses/prediction.py``) and the clustering metrics it prints.
-Plots and decompositions are not part of this build."""
+on a model: label prediction from the latent representation
+(``scvae/analyses/prediction.py``) with the clustering metrics it prints, and
+the summary statistics of the evaluation set and of its reconstruction, the
+metrics table of ``analyse_results`` (``scvae/analyses/metrics/summary.py``).
+The ``analyse`` command, the metrics files, plots and decompositions are not
+part of this build."""
 from scvae_amd.analyses.prediction import (  # noqa: F401
     PREDICTION_METHODS, PredictionSpecifications, predict_labels,
     map_cluster_ids_to_label_ids)
@@ -9,3 +12,5 @@ from scvae_amd.analyses.silhouette import (  # noqa: F401
     silhouette_samples, silhouette_score)
 from scvae_amd.analyses.count_silhouette import (  # noqa: F401
     count_silhouette_samples, count_silhouette_score)
+from scvae_amd.analyses.summary import (  # noqa: F401
+    comparison_statistics, format_summary_statistics, summary_statistics)

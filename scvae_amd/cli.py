@@ -22,7 +22,8 @@ from scvae_amd.models import (
     GaussianMixtureVariationalAutoencoder, VariationalAutoencoder)
 from scvae_amd.models.utilities import (
     better_model_exists, model_stopped_early)
-from scvae_amd.utilities import normalise_string, subtitle, title
+from scvae_amd.utilities import (
+    format_duration, normalise_string, subtitle, title)
 
 
 def _setup_model(data_set, model_type=None, latent_size=None,
@@ -210,8 +211,19 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              sample_size=None, model_versions=None, prediction_method=None,
              prediction_training_set_kind=None, prediction_on_device=False,
              silhouette_score=False, silhouette_space="latent",
+             summary_statistics=False, analysis_level=None,
              **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
+
+    ``summary_statistics`` (not in the reference's ``evaluate``, which leaves
+    it to ``analyse_results``): after the evaluation of each model version
+    print the metrics table of ``analyses/analyses.py:873-895, 1040`` -- mean,
+    standard deviation, dispersion, minimum, maximum and sparsity of the
+    evaluation set and of the reconstructed set -- computed on the GPU in one
+    pass over the reconstruction where it lies (``analyses/summary.py``).
+    ``analysis_level`` (the reference's option, read only with
+    ``summary_statistics``): ``"extensive"`` adds the rows ``differences`` and
+    ``log-ratios``.
 
     ``prediction_on_device`` (not in the reference): run the k-means of the
     prediction on the GPU (``analyses/kmeans.py``: exact Lloyd for every
@@ -234,6 +246,16 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     if silhouette_score and silhouette_space not in ("latent", "counts"):
         raise ValueError("Silhouette space `{}` not found.".format(
             silhouette_space))
+    summary_level = None
+    if summary_statistics:
+        if analysis_level is None:
+            analysis_level = defaults["analyses"]["analysis_level"]
+        analysis_level = normalise_string(str(analysis_level))
+        if analysis_level not in ("limited", "normal", "extensive"):
+            raise ValueError("Analysis level `{}` not found.".format(
+                analysis_level))
+        summary_level = ("extensive" if analysis_level == "extensive"
+                         else "normal")
     if prediction_method is None:
         prediction_method = defaults["evaluation"]["prediction_method"]
     if prediction_training_set_kind is None:
@@ -342,7 +364,11 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             minibatch_size=minibatch_size, run_id=run_id,
             use_best_model=use_best_model,
             use_early_stopping_model=use_early_stopping_model,
-            output_versions="all")
+            output_versions="all",
+            **({"summary_statistics": summary_level} if summary_level
+               else {}))
+        if summary_level:   # analyses.py:873-899, 1040-1041
+            _print_summary_statistics(results[model_version][1])
         print()
         if sample_size:   # cli.py:494-505
             print(subtitle("Sampling ({})".format(
@@ -362,6 +388,23 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
                      silhouette_score=bool(silhouette_score),
                      silhouette_space=silhouette_space)
     return results
+
+
+def _print_summary_statistics(reconstructed_set):
+    """The metrics table of ``analyse_results`` (``analyses.py:873, 898-899,
+    1040``) from the rows ``model.evaluate`` attached to the reconstructed
+    set.  The rows were computed inside the evaluation, before the
+    reconstruction left the device; the duration is that of the pass.  With
+    several ranks only rank 0 has them: the others print nothing."""
+    from scvae_amd.analyses.summary import format_summary_statistics
+    statistics = getattr(reconstructed_set, "summary_statistics", None)
+    if statistics is None:
+        return
+    print("Calculating metrics for results.")
+    print("Metrics calculated ({}).".format(format_duration(
+        getattr(reconstructed_set, "summary_statistics_duration", 0.0))))
+    print()
+    print(format_summary_statistics(statistics))
 
 
 def _predict(model, version_results, prediction_training_set, specifications,
@@ -686,6 +729,20 @@ def main(arguments=None):
              "counts of the evaluation set, 20 000 cells sampled above "
              "20 000, with exact distances on the GPU (integer counts below "
              "65 536, at most 65 536 genes, else scikit-learn on the host)")
+    parser_evaluate.add_argument(
+        "--summary-statistics", action="store_true", default=False,
+        help="(this build) after the evaluation of each model version, print "
+             "the metrics table of the reference's analyses: mean, standard "
+             "deviation, dispersion, minimum, maximum and sparsity of the "
+             "evaluation set and of the reconstructed set, computed on the "
+             "GPU in one pass before the reconstruction leaves it")
+    parser_evaluate.add_argument(
+        "--analysis-level",
+        choices=["limited", "normal", "extensive"],
+        default=_parse_default(defaults["analyses"]["analysis_level"]),
+        help="with --summary-statistics: limited, normal, or extensive, "
+             "which adds the rows of the differences and of the log-ratios "
+             "between the reconstructed and the evaluation set")
     parser_evaluate.add_argument(
         "--model-versions", metavar="VERSION", nargs="+",
         default=_parse_default(defaults["evaluation"]["model_versions"]),

@@ -1304,6 +1304,23 @@ class ModelBase:
             evaluation_subset_indices = set()
         log_results = kwargs.get("log_results", True)
         use_deterministic_z = kwargs.get("use_deterministic_z", False)
+        # (not in the reference's signature) the rows of the metrics table of
+        # analyse_results (analyses.py:873-895), attached to the returned
+        # reconstructed set as ``summary_statistics``: None / False, True /
+        # "normal", or "extensive" (also differences and log-ratios)
+        summary_level = kwargs.get("summary_statistics")
+        if summary_level is None or summary_level is False:
+            summary_level = None
+        elif summary_level is True:
+            summary_level = "normal"
+        elif summary_level not in ("normal", "extensive"):
+            raise ValueError(
+                "Summary statistics `{}` not found: None, False, True, "
+                "\"normal\" or \"extensive\".".format(summary_level))
+        if summary_level and "reconstructed" not in output_versions:
+            raise ValueError(
+                "Summary statistics need the reconstructed set: "
+                "\"reconstructed\" must be in the output versions.")
 
         minibatch_size = self._training_minibatch_size(
             minibatch_size, "evaluation")
@@ -1406,6 +1423,20 @@ class ModelBase:
                 preprocessing_methods=evaluation_set.preprocessing_methods,
                 kind=evaluation_set.kind, version=version, **extra)
 
+        summary_rows = None
+        if summary_level and master:
+            # over p_x_mean where it lies, before its copy to the host; the
+            # original side is what the likelihood saw (t_eval: the
+            # reference's transformed set), gathered in blocks of rows
+            from scvae_amd.analyses.summary import evaluation_statistics
+            summary_time_start = time()
+            summary_rows = evaluation_statistics(
+                t_eval, outputs["p_x_mean"],
+                names=("transformed" if t_eval.transformed_values is not None
+                       else evaluation_set.version, "reconstructed"),
+                extensive=summary_level == "extensive")
+            summary_duration = time() - summary_time_start
+
         output_sets = [None] * len(output_versions)
         if "transformed" in output_versions:
             # (va:2135-2158: the binarised / noisily preprocessed values the
@@ -1433,6 +1464,12 @@ class ModelBase:
                 p_x_mean_eval, "reconstructed",
                 total_standard_deviations=p_x_stddev_eval,
                 explained_standard_deviations=stddev_of_p_x_mean_eval)
+            if summary_rows is not None:
+                reconstructed_set = output_sets[
+                    output_versions.index("reconstructed")]
+                reconstructed_set.summary_statistics = summary_rows
+                reconstructed_set.summary_statistics_duration = (
+                    summary_duration)
         if "latent" in output_versions:
             latent_names = numpy.array([
                 "latent variable {}".format(i + 1)
