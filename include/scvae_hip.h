@@ -799,6 +799,34 @@ int scvae_summary_accumulate(const float* recon, int64_t ldr, const float* orig,
 int scvae_summary_finish(const void* workspace, int64_t workspace_bytes, double* stats,
                          int64_t* counts, void* stream);
 
+/* ---- principal components of a cells x genes matrix by block subspace iteration: the passes
+ *      over the matrix that scvae_amd/analyses/decomposition.py iterates, in place of the
+ *      IncrementalPCA(batch_size=100) that the reference fits for more than 2000 features or a
+ *      sparse matrix (scvae/analyses/decomposition/decomposition.py:65-91, incremental_pca.py;
+ *      called from analyses/subanalyses.py:655-674 for analyses/analyses.py:1237-1280).
+ *      x [rows, F] fp32 with row pitch ldx >= F in elements, unit column stride, 4-byte aligned,
+ *      read in place (columns F .. ldx - 1 are never read); 1 <= rows <= 2^31 - 1,
+ *      1 <= F <= 2^20, 1 <= b <= 32; anything else returns -1 and scvae_last_error() names it.
+ *      With Xc = X - 1 mu^T: every element is converted to fp64 and mu_j subtracted from it in
+ *      registers; the products run on the fp64 matrix cores and accumulate in fp64.  No atomics,
+ *      one fixed order of every sum: the same input gives the same bits on every run.  mu, q, y,
+ *      z and total are DEVICE fp64, 8-byte aligned; q [F, b], y [rows, b] and z [F, b] are
+ *      row-major without padding. ---- */
+/* bytes of the 8-byte aligned workspace that scvae_pca_moments and scvae_pca_back_project take
+ * for these sizes (the partial sums of the ranges the rows are split in); -1 for bad sizes */
+int64_t scvae_pca_workspace_bytes(int64_t rows, int64_t F, int64_t b);
+/* mu[j] = the mean of column j, *total = sum_ij (x_ij - mu_j)^2 from a second pass over the
+ * deviations (not sum x^2 - rows mu^2).  workspace: as for b = 1. */
+int scvae_pca_moments(const float* x, int64_t ldx, int64_t rows, int64_t F, double* mu,
+                      double* total, void* workspace, int64_t workspace_bytes, void* stream);
+/* y = Xc q: the step Y = Xc Q of the iteration, and `transform` (decomposition.py:91, 97) */
+int scvae_pca_project(const float* x, int64_t ldx, int64_t rows, int64_t F, const double* mu,
+                      const double* q, int64_t b, double* y, void* stream);
+/* z = Xc^T y */
+int scvae_pca_back_project(const float* x, int64_t ldx, int64_t rows, int64_t F, const double* mu,
+                           const double* y, int64_t b, double* z, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

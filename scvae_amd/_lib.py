@@ -331,6 +331,16 @@ SIGNATURES = {
         c_int32, c_void_p, c_int64, c_void_p]),
     "scvae_summary_finish": (c_int32, [
         c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "scvae_pca_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "scvae_pca_moments": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+        c_int64, c_void_p]),
+    "scvae_pca_project": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+        c_void_p, c_void_p]),
+    "scvae_pca_back_project": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+        c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -23,7 +23,7 @@ from scvae_amd.models import (
 from scvae_amd.models.utilities import (
     better_model_exists, model_stopped_early)
 from scvae_amd.utilities import (
-    format_duration, normalise_string, subtitle, title)
+    capitalise_string, format_duration, normalise_string, subtitle, title)
 
 
 def _setup_model(data_set, model_type=None, latent_size=None,
@@ -212,8 +212,19 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              prediction_training_set_kind=None, prediction_on_device=False,
              silhouette_score=False, silhouette_space="latent",
              summary_statistics=False, analysis_level=None,
-             **keyword_arguments):
+             decompositions=False, decomposition_methods=None,
+             analyses_directory=None, **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
+
+    ``decompositions`` (not in the reference's ``evaluate``, which leaves it
+    to ``analyse_results``): after the evaluation of each model version the
+    two-component PCA of the reconstructed set (``analyses.py:1237-1252``),
+    fitted on the GPU on the reconstruction where it lies
+    (``analyses/decomposition.py``); with ``analysis_level="extensive"`` also
+    the reconstructions in the space of the originals
+    (``analyses.py:1267-1280``).  The coordinates go to tab-separated files
+    under ``analyses_directory``.  ``decomposition_methods`` (the reference's
+    option): only ``pca`` is built.
 
     ``summary_statistics`` (not in the reference's ``evaluate``, which leaves
     it to ``analyse_results``): after the evaluation of each model version
@@ -246,16 +257,29 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     if silhouette_score and silhouette_space not in ("latent", "counts"):
         raise ValueError("Silhouette space `{}` not found.".format(
             silhouette_space))
-    summary_level = None
-    if summary_statistics:
+    summary_level = decomposition_level = None
+    if summary_statistics or decompositions:
         if analysis_level is None:
             analysis_level = defaults["analyses"]["analysis_level"]
         analysis_level = normalise_string(str(analysis_level))
         if analysis_level not in ("limited", "normal", "extensive"):
             raise ValueError("Analysis level `{}` not found.".format(
                 analysis_level))
-        summary_level = ("extensive" if analysis_level == "extensive"
-                         else "normal")
+        level = "extensive" if analysis_level == "extensive" else "normal"
+        if summary_statistics:
+            summary_level = level
+        if decompositions:
+            decomposition_level = level
+    if decomposition_level:
+        from scvae_amd.analyses.decomposition import method_name
+        if decomposition_methods is None:
+            decomposition_methods = [
+                defaults["analyses"]["decomposition_method"]]
+        elif not isinstance(decomposition_methods, (list, tuple)):
+            decomposition_methods = [decomposition_methods]
+        decomposition_methods = [method_name(m) for m in decomposition_methods]
+        if analyses_directory is None:
+            analyses_directory = defaults["analyses"]["directory"]
     if prediction_method is None:
         prediction_method = defaults["evaluation"]["prediction_method"]
     if prediction_training_set_kind is None:
@@ -366,10 +390,14 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             use_early_stopping_model=use_early_stopping_model,
             output_versions="all",
             **({"summary_statistics": summary_level} if summary_level
+               else {}),
+            **({"decompositions": decomposition_level}
+               if decomposition_level and "PCA" in decomposition_methods
                else {}))
         if summary_level:   # analyses.py:873-899, 1040-1041
             _print_summary_statistics(results[model_version][1])
         print()
+        sample_reconstruction_set = None
         if sample_size:   # cli.py:494-505
             print(subtitle("Sampling ({})".format(
                 model_version.replace("_", " "))))
@@ -380,6 +408,19 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             results[model_version] = (
                 results[model_version], sample_reconstruction_set)
             print()
+        if decomposition_level:   # analyses.py:1237-1280
+            evaluation_results = (results[model_version][0] if sample_size
+                                  else results[model_version])
+            _report_decompositions(
+                evaluation_results[1], decomposition_methods,
+                sample_reconstruction_set,
+                _decompositions_directory(
+                    build_directory_path(
+                        analyses_directory, data_set=data_set,
+                        splitting_method=splitting_method,
+                        splitting_fraction=splitting_fraction),
+                    model, evaluation_set, run_id, use_best_model,
+                    use_early_stopping_model))
         if prediction_specifications is not None:   # cli.py:509-543
             _predict(model, results[model_version], prediction_training_set,
                      prediction_specifications, minibatch_size, run_id,
@@ -405,6 +446,96 @@ def _print_summary_statistics(reconstructed_set):
         getattr(reconstructed_set, "summary_statistics_duration", 0.0))))
     print()
     print(format_summary_statistics(statistics))
+
+
+def _decompositions_directory(base_directory, model, evaluation_set, run_id,
+                              best_model, early_stopping):
+    """Where the analyses of one evaluation go, laid out as the reference
+    lays them out (``analyses.py:804-830, 1609-1630``):
+    ``<base>/<model>/[run_<id>/]e_<epochs>[-early_stopping|-best_model]-mc_<n>
+    -iw_<n>/[<kind>/]``, the kind for every set but the test set."""
+    from scvae_amd.models.utilities import (
+        check_run_id, load_number_of_epochs_trained)
+    if run_id is None:
+        run_id = defaults["models"]["run_id"]
+    parts = ["e_{}".format(load_number_of_epochs_trained(
+        model, run_id=run_id, early_stopping=early_stopping,
+        best_model=best_model))]
+    if early_stopping:
+        parts.append("early_stopping")
+    elif best_model:
+        parts.append("best_model")
+    parts.append("mc_{}".format(
+        model.number_of_monte_carlo_samples["evaluation"]))
+    parts.append("iw_{}".format(
+        model.number_of_importance_samples["evaluation"]))
+    directory = os.path.join(base_directory, model.name)
+    if run_id:
+        directory = os.path.join(
+            directory, "run_{}".format(check_run_id(run_id)))
+    directory = os.path.join(directory, "-".join(parts))
+    if evaluation_set.kind != "test":
+        directory = os.path.join(directory, evaluation_set.kind)
+    return directory
+
+
+def _write_coordinates(path, data_set, coordinates):
+    """Example name, PC 1, PC 2 and, where the set has labels, the label:
+    tab-separated."""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    names = getattr(data_set, "example_names", None)
+    labels = (data_set.labels if getattr(data_set, "has_labels", False)
+              else None)
+    with open(path, "w") as file:
+        file.write("\t".join(["example", "PC 1", "PC 2"]
+                             + (["label"] if labels is not None else []))
+                   + "\n")
+        for i, row in enumerate(coordinates):
+            fields = [str(names[i]) if names is not None else str(i),
+                      repr(float(row[0])), repr(float(row[1]))]
+            if labels is not None:
+                fields.append(str(labels[i]))
+            file.write("\t".join(fields) + "\n")
+
+
+def _report_decompositions(reconstructed_set, methods, sampled_set,
+                           directory):
+    """The lines of ``analyse_decompositions`` (``subanalyses.py:655-674``)
+    for the fits ``model.evaluate`` attached to the reconstructed set, one
+    line with the explained-variance ratios and the iteration count of each,
+    and the files of coordinates.  With several ranks only rank 0 has the
+    fits: the others print nothing."""
+    for method in methods:
+        if method != "PCA":
+            print("Decomposition method `{}` is not built: skipped.".format(
+                method))
+    if "PCA" not in methods:
+        return
+    fits = [
+        ("decomposition", "reconstructions set", "reconstructions"),
+        ("decomposition_in_original_space",
+         "reconstructed set values in originals set",
+         "reconstructed-originals")]
+    for attribute, fit_title, name in fits:
+        fit = getattr(reconstructed_set, attribute, None)
+        if fit is None:
+            continue
+        print("Decomposing {} using PCA.".format(fit_title))
+        print("{} decomposed ({}).".format(
+            capitalise_string(fit_title), format_duration(fit["duration"])))
+        print("    Explained variance ratios: {}; {} iterations{}.".format(
+            ", ".join("{:.5g}".format(ratio)
+                      for ratio in fit["explained_variance_ratio"]),
+            fit["iterations"],
+            "" if fit["converged"] else " (not converged)"))
+        print()
+        _write_coordinates(os.path.join(directory, name, "pca.tsv"),
+                           reconstructed_set, fit["coordinates"])
+        if sampled_set is not None and attribute == "decomposition":
+            # (analyses.py:1244: the sampled set in the fitted space)
+            _write_coordinates(
+                os.path.join(directory, name, "pca-sampled.tsv"), sampled_set,
+                fit["model"].transform(sampled_set.values))
 
 
 def _predict(model, version_results, prediction_training_set, specifications,
@@ -742,7 +873,22 @@ def main(arguments=None):
         default=_parse_default(defaults["analyses"]["analysis_level"]),
         help="with --summary-statistics: limited, normal, or extensive, "
              "which adds the rows of the differences and of the log-ratios "
-             "between the reconstructed and the evaluation set")
+             "between the reconstructed and the evaluation set; with "
+             "--decompositions: extensive adds the reconstructions in the "
+             "space of the originals")
+    parser_evaluate.add_argument(
+        "--decompositions", action="store_true", default=False,
+        help="(this build) after the evaluation of each model version, fit "
+             "the two-component PCA of the reconstructed set on the GPU "
+             "before the reconstruction leaves it (the converged exact PCA "
+             "where the reference fits an incremental one), print its "
+             "explained-variance ratios and write the coordinates of every "
+             "example to a tab-separated file under --analyses-directory")
+    parser_evaluate.add_argument(
+        "--decomposition-methods", metavar="METHOD", nargs="+",
+        default=_parse_default(defaults["analyses"]["decomposition_method"]),
+        help="with --decompositions: methods to decompose with (only pca is "
+             "built)")
     parser_evaluate.add_argument(
         "--model-versions", metavar="VERSION", nargs="+",
         default=_parse_default(defaults["evaluation"]["model_versions"]),

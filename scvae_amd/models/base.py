@@ -1321,6 +1321,23 @@ class ModelBase:
             raise ValueError(
                 "Summary statistics need the reconstructed set: "
                 "\"reconstructed\" must be in the output versions.")
+        # (not in the reference's signature) the two-component PCA of
+        # analyse_results' "Decompositions" (analyses.py:1237-1280), attached
+        # to the returned reconstructed set as ``decomposition`` and, with
+        # "extensive", ``decomposition_in_original_space``
+        decomposition_level = kwargs.get("decompositions")
+        if decomposition_level is None or decomposition_level is False:
+            decomposition_level = None
+        elif decomposition_level is True:
+            decomposition_level = "normal"
+        elif decomposition_level not in ("normal", "extensive"):
+            raise ValueError(
+                "Decompositions `{}` not found: None, False, True, "
+                "\"normal\" or \"extensive\".".format(decomposition_level))
+        if decomposition_level and "reconstructed" not in output_versions:
+            raise ValueError(
+                "Decompositions need the reconstructed set: "
+                "\"reconstructed\" must be in the output versions.")
 
         minibatch_size = self._training_minibatch_size(
             minibatch_size, "evaluation")
@@ -1437,6 +1454,21 @@ class ModelBase:
                 extensive=summary_level == "extensive")
             summary_duration = time() - summary_time_start
 
+        decompositions = {}
+        if decomposition_level and master:
+            # fitted on p_x_mean where it lies, before its copy to the host
+            from scvae_amd.analyses.decomposition import (
+                densify, evaluation_decomposition)
+            decompositions["decomposition"] = evaluation_decomposition(
+                outputs["p_x_mean"])
+            if decomposition_level == "extensive":
+                # the original side is what the likelihood saw (t_eval); the
+                # reconstruction is projected into its space
+                # (analyses.py:1267-1280)
+                decompositions["decomposition_in_original_space"] = (
+                    evaluation_decomposition(
+                        densify(t_eval), projected=outputs["p_x_mean"]))
+
         output_sets = [None] * len(output_versions)
         if "transformed" in output_versions:
             # (va:2135-2158: the binarised / noisily preprocessed values the
@@ -1470,6 +1502,9 @@ class ModelBase:
                 reconstructed_set.summary_statistics = summary_rows
                 reconstructed_set.summary_statistics_duration = (
                     summary_duration)
+            for name, decomposition in decompositions.items():
+                setattr(output_sets[output_versions.index("reconstructed")],
+                        name, decomposition)
         if "latent" in output_versions:
             latent_names = numpy.array([
                 "latent variable {}".format(i + 1)
