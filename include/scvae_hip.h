@@ -827,6 +827,48 @@ int scvae_pca_back_project(const float* x, int64_t ldx, int64_t rows, int64_t F,
                            const double* y, int64_t b, double* z, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- exact t-SNE of the latent values: the passes that scvae_amd/analyses/tsne.py iterates, in
+ *      place of the Barnes-Hut sklearn.manifold.TSNE that the reference fits on the host
+ *      (scvae/analyses/decomposition/decomposition.py:78-91, called from
+ *      analyses/subanalyses.py:595-673 for analyses/analyses.py:1405-1416).  The objective and
+ *      the optimiser are scikit-learn's TSNE(method="exact"): two components, Euclidean metric,
+ *      one degree of freedom.  x [N, L] fp32 with row pitch ldx >= L, read in place;
+ *      1 <= L <= 128, 2 <= N <= 2^22; anything else returns -1 and scvae_last_error() names it.
+ *      d2(i, j) = sum_l (x_il - x_jl)^2 in the direct form in fp32.  The joint probabilities are
+ *      never stored: each pass forms them per pair from the rows, beta and row_sum.  No atomics,
+ *      one fixed order of every sum: the same inputs give the same bits on every run. ---- */
+/* bytes of the 8-byte aligned workspace that scvae_tsne_perplexity and scvae_tsne_gradient
+ * share for these sizes: the squared distances of up to 512 rows at a time for the search,
+ * the rows' partial sums for a pass */
+int64_t scvae_tsne_workspace_bytes(int64_t N, int64_t L);
+/* scikit-learn's _binary_search_perplexity for every row i over p(j | i) = exp(-beta_i d2(i, j)),
+ * j != i: beta from 1, doubled or halved until bracketed, then bisected, at most 100 steps, until
+ * |H - log(perplexity)| <= 1e-5.  beta[N] fp32 (held in fp32 throughout the search),
+ * row_sum[N] fp32 = sum_j p(j | i) at that beta (1e-8 where every term is 0, as scikit-learn
+ * sets it; exp() is fp32: a term below 2^-126 is 0), steps[N] int32 = the bisection steps
+ * taken, 100 where the tolerance was not reached (beta is then the last one tested).  On
+ * return the first N doubles of the workspace hold sum_j p(j | i) / row_sum[i] of every row:
+ * their sum, doubled, is sum_p below. */
+int scvae_tsne_perplexity(const float* x, int64_t ldx, int64_t N, int64_t L, double perplexity,
+                          float* beta, float* row_sum, int32_t* steps, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+/* One pass over all pairs at the embedding y [N, 2] fp32:
+ * P_ij = max((exp(-beta_i d2) / row_sum[i] + exp(-beta_j d2) / row_sum[j]) / sum_p, 2^-52)
+ * exaggeration, w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij,
+ * grad[i] = 4 (sum_j P_ij w_ij (y_i - y_j) - sum_j w_ij^2 (y_i - y_j) / Z), [N, 2] fp32.
+ * *grad_norm (device fp64, optional) = |grad|.  *kl (device fp64, optional: a second pass over
+ * all pairs) = sum_{i != j} P_ij log(P_ij / max(w_ij / Z, 2^-52)).  The rows' sums, Z, the KL
+ * divergence and the norm are added in fp64. */
+int scvae_tsne_gradient(const float* x, int64_t ldx, int64_t N, int64_t L, const float* beta,
+                        const float* row_sum, double sum_p, const float* y, float exaggeration,
+                        float* grad, double* kl, double* grad_norm, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* scikit-learn's _gradient_descent step on [N, 2] fp32: gains + 0.2 where update grad < 0, else
+ * gains 0.8, at least min_gain; update = momentum update - learning_rate gains grad;
+ * y += update */
+int scvae_tsne_update(float* y, float* update, float* gains, const float* grad, int64_t N,
+                      float momentum, float learning_rate, float min_gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

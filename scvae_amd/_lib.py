@@ -341,6 +341,17 @@ SIGNATURES = {
     "scvae_pca_back_project": (c_int32, [
         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
         c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_tsne_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "scvae_tsne_perplexity": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_double, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_tsne_gradient": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_double,
+        c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+        c_void_p]),
+    "scvae_tsne_update": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+        c_float, c_void_p]),
 }
 
 _lib = None

@@ -3,10 +3,11 @@ on a model: label prediction from the latent representation
 (``scvae/analyses/prediction.py``) with the clustering metrics it prints, and
 the summary statistics of the evaluation set and of its reconstruction, the
 metrics table of ``analyse_results`` (``scvae/analyses/metrics/summary.py``),
-and the PCA of its "Decompositions"
-(``scvae/analyses/decomposition/decomposition.py``).  The ``analyse`` command,
-the metrics files, plots and the other decomposition methods are not part of
-this build."""
+the PCA of its "Decompositions"
+(``scvae/analyses/decomposition/decomposition.py``), and the t-SNE map of its
+"latent space" (``scvae/analyses/subanalyses.py:595-673``).  The ``analyse``
+command, the metrics files, plots and the other decomposition methods are not
+part of this build."""
 from scvae_amd.analyses.prediction import (  # noqa: F401
     PREDICTION_METHODS, PredictionSpecifications, predict_labels,
     map_cluster_ids_to_label_ids)
@@ -18,3 +19,5 @@ from scvae_amd.analyses.summary import (  # noqa: F401
     comparison_statistics, format_summary_statistics, summary_statistics)
 from scvae_amd.analyses.decomposition import (  # noqa: F401
     DevicePCA, decompose)
+from scvae_amd.analyses.tsne import (  # noqa: F401
+    DeviceTSNE, decompose_latent)

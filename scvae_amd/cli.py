@@ -213,7 +213,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              silhouette_score=False, silhouette_space="latent",
              summary_statistics=False, analysis_level=None,
              decompositions=False, decomposition_methods=None,
-             analyses_directory=None, **keyword_arguments):
+             latent_space=False, analyses_directory=None,
+             **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
 
     ``decompositions`` (not in the reference's ``evaluate``, which leaves it
@@ -225,6 +226,16 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     (``analyses.py:1267-1280``).  The coordinates go to tab-separated files
     under ``analyses_directory``.  ``decomposition_methods`` (the reference's
     option): only ``pca`` is built.
+
+    ``latent_space`` (not in the reference's ``evaluate``, which leaves it to
+    ``analyse_results``): after the evaluation of each model version, the
+    two-dimensional maps of every latent set with more than two features
+    (``analyses.py:1405-1416``, ``subanalyses.py:595-673``), one for every
+    method in ``decomposition_methods``: ``pca`` as above, ``t-SNE`` exact
+    over every pair of cells on the GPU (``analyses/tsne.py``) where the
+    reference fits the Barnes-Hut approximation on the host.  The coordinates
+    go to tab-separated files under ``analyses_directory``.  With several
+    ranks only rank 0 fits and writes (not tested on more than one GPU).
 
     ``summary_statistics`` (not in the reference's ``evaluate``, which leaves
     it to ``analyse_results``): after the evaluation of each model version
@@ -270,7 +281,7 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             summary_level = level
         if decompositions:
             decomposition_level = level
-    if decomposition_level:
+    if decomposition_level or latent_space:
         from scvae_amd.analyses.decomposition import method_name
         if decomposition_methods is None:
             decomposition_methods = [
@@ -408,19 +419,24 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             results[model_version] = (
                 results[model_version], sample_reconstruction_set)
             print()
-        if decomposition_level:   # analyses.py:1237-1280
+        if decomposition_level or latent_space:
             evaluation_results = (results[model_version][0] if sample_size
                                   else results[model_version])
+            version_directory = _decompositions_directory(
+                build_directory_path(
+                    analyses_directory, data_set=data_set,
+                    splitting_method=splitting_method,
+                    splitting_fraction=splitting_fraction),
+                model, evaluation_set, run_id, use_best_model,
+                use_early_stopping_model)
+        if decomposition_level:   # analyses.py:1237-1280
             _report_decompositions(
                 evaluation_results[1], decomposition_methods,
-                sample_reconstruction_set,
-                _decompositions_directory(
-                    build_directory_path(
-                        analyses_directory, data_set=data_set,
-                        splitting_method=splitting_method,
-                        splitting_fraction=splitting_fraction),
-                    model, evaluation_set, run_id, use_best_model,
-                    use_early_stopping_model))
+                sample_reconstruction_set, version_directory)
+        if latent_space:   # analyses.py:1405-1416
+            _report_latent_space(
+                evaluation_results[2], decomposition_methods,
+                version_directory)
         if prediction_specifications is not None:   # cli.py:509-543
             _predict(model, results[model_version], prediction_training_set,
                      prediction_specifications, minibatch_size, run_id,
@@ -479,15 +495,16 @@ def _decompositions_directory(base_directory, model, evaluation_set, run_id,
     return directory
 
 
-def _write_coordinates(path, data_set, coordinates):
-    """Example name, PC 1, PC 2 and, where the set has labels, the label:
-    tab-separated."""
+def _write_coordinates(path, data_set, coordinates, column_label="PC"):
+    """Example name, the two coordinates (``PC 1``, ``PC 2``) and, where the
+    set has labels, the label: tab-separated."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
     names = getattr(data_set, "example_names", None)
     labels = (data_set.labels if getattr(data_set, "has_labels", False)
               else None)
     with open(path, "w") as file:
-        file.write("\t".join(["example", "PC 1", "PC 2"]
+        file.write("\t".join(["example", column_label + " 1",
+                              column_label + " 2"]
                              + (["label"] if labels is not None else []))
                    + "\n")
         for i, row in enumerate(coordinates):
@@ -536,6 +553,45 @@ def _report_decompositions(reconstructed_set, methods, sampled_set,
             _write_coordinates(
                 os.path.join(directory, name, "pca-sampled.tsv"), sampled_set,
                 fit["model"].transform(sampled_set.values))
+
+
+def _report_latent_space(latent_sets, methods, directory):
+    """The "latent space" group of ``analyse_results``
+    (``analyses.py:1405-1416``): for every latent set with more than two
+    features and every method the lines of ``analyse_decompositions``
+    (``subanalyses.py:595-674``), for t-SNE one line with the KL divergence
+    and the iteration count, and the file of coordinates,
+    ``latent_space-<version>/<method>.tsv``.  With several ranks only rank 0
+    fits and writes."""
+    import torch.distributed as dist
+    from scvae_amd.analyses.decomposition import DECOMPOSITION_METHOD_LABEL
+    from scvae_amd.analyses.tsne import decompose_latent
+    if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+        return
+    for method in methods:
+        if method not in ("PCA", "t-SNE"):
+            print("Decomposition method `{}` is not built: skipped.".format(
+                method))
+    for version, latent_set in latent_sets.items():
+        if latent_set.values.shape[1] <= 2:
+            continue
+        set_title = "latent space for {} set".format(version)
+        for method in methods:
+            if method not in ("PCA", "t-SNE"):
+                continue
+            fit = decompose_latent(latent_set.values, method, set_title)
+            if fit is None:
+                continue
+            model = fit["model"]
+            if hasattr(model, "kl_divergence_"):
+                print("    KL divergence: {:.5g}; {} iterations.".format(
+                    model.kl_divergence_, model.n_iter_ + 1))
+            print()
+            _write_coordinates(
+                os.path.join(directory, "latent_space-{}".format(version),
+                             normalise_string(method) + ".tsv"),
+                latent_set, fit["coordinates"],
+                column_label=DECOMPOSITION_METHOD_LABEL[method])
 
 
 def _predict(model, version_results, prediction_training_set, specifications,
@@ -888,7 +944,17 @@ def main(arguments=None):
         "--decomposition-methods", metavar="METHOD", nargs="+",
         default=_parse_default(defaults["analyses"]["decomposition_method"]),
         help="with --decompositions: methods to decompose with (only pca is "
-             "built)")
+             "built); with --latent-space: pca and t-SNE")
+    parser_evaluate.add_argument(
+        "--latent-space", action="store_true", default=False,
+        help="(this build) after the evaluation of each model version, the "
+             "two-dimensional maps of every latent set with more than two "
+             "features, one for every method in --decomposition-methods: "
+             "pca, or t-SNE exact over every pair of cells on the GPU "
+             "(scikit-learn's exact objective and schedule where the "
+             "reference fits the Barnes-Hut approximation on the host; 4 to "
+             "200 000 cells), their coordinates in tab-separated files "
+             "under --analyses-directory")
     parser_evaluate.add_argument(
         "--model-versions", metavar="VERSION", nargs="+",
         default=_parse_default(defaults["evaluation"]["model_versions"]),
