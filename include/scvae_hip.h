@@ -672,7 +672,9 @@ int scvae_iw_logmeanexp(const float* ll, const float* kl_cell, int32_t kl_per_sa
  * pre-activations pre_j [S*B, F] the mean of p(x|z) averaged over the samples (p_x_mean), the
  * sample mean of its variance (mean_of_var) and the variance of its mean over the samples
  * (var_of_mean), each [B, F].  weight (optional, [B] with stride ldw) and accumulate != 0 form
- * the GMVAE's mixture sums over the clusters (gm:3311-3386). */
+ * the GMVAE's mixture sums over the clusters (gm:3311-3386).  Every element-wise kind; for the
+ * constrained Poisson pre_0 is the rate lambda * N itself.  Variances are sums of non-negative
+ * terms (never negative), +inf where the value is above the fp32 maximum. */
 int scvae_pxmean_stats(int32_t kind, const float* const* pre, int64_t S, int64_t B, int64_t F,
                        const float* weight, int64_t ldw, int32_t accumulate, float* p_x_mean,
                        float* mean_of_var, float* var_of_mean, void* stream);

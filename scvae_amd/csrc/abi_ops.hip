@@ -337,7 +337,8 @@ int scvae_iw_logmeanexp(const float* ll, const float* kl_cell, int32_t kl_per_sa
 int scvae_pxmean_stats(int32_t kind, const float* const* pre, int64_t S, int64_t B, int64_t F,
                        const float* weight, int64_t ldw, int32_t accumulate, float* p_x_mean,
                        float* mean_of_var, float* var_of_mean, void* stream) {
-  SCVAE_ARG(pre && ((kind >= 0 && kind <= 3) || kind == LK_BERNOULLI) && S > 0 && B >= 0 && F > 0);
+  // (constrained Poisson: head 0 is the rate lambda * N, as px_statistics takes it in a step)
+  SCVAE_ARG(pre && kind >= 0 && kind <= LK_BERNOULLI && S > 0 && B >= 0 && F > 0);
   scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
   for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = const_cast<float*>(pre[j]);
   return scvae::px_statistics((hipStream_t)stream, kind, hp, (int)F, (int)S, (int)B, (int)F,

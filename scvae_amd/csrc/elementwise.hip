@@ -285,24 +285,38 @@ int loglik_cat_bwd(hipStream_t stream, int kind, const float* t, int ldt, HeadPt
   return launch_loglik_cat<true>(stream, kind, t, ldt, pre, ldp, logits, K, gw, ll, rows, B, F);
 }
 
-// mean and variance of Categorised(dist, cat) (categorised.py:210-253)
+// mean and variance of Categorised(dist, cat) (categorised.py:210-253), K + 1 <= 65 classes.
+// The reference's second moment minus mean^2 loses the variance of a confident class in fp32
+// (and goes negative); here it is the centred sum of non-negative terms
+//   sum_{c<K} pi_c (c - mean)^2 + pi_K (v + d^2),   d = K + m - mean = sum_{c<K} pi_c (K + m - c)
+// over the unnormalised e_c = exp(l_c - max), in two passes over the logits.
 template <int KIND>
 __device__ __forceinline__ void cat_mean_var(const float* a, const float* __restrict__ l, int K,
                                              float& mean, float& var) {
-  const int C = K + 1;
-  const float lse = cat_log_normaliser(l, C);
-  float m1 = 0.f, m2 = 0.f;
+  float top = l[0];
+  for (int c = 1; c <= K; ++c) top = fmaxf(top, l[c]);
+  float dm, dq;
+  lik_mean_dispersion<KIND>(a, dm, dq);
+  const float km = (float)K + dm;
+  float s0 = 0.f, s1 = 0.f, sd = 0.f;
   for (int c = 0; c < K; ++c) {
-    const float pi = __expf(l[c] - lse);
-    m1 += (float)c * pi;
-    m2 += (float)(c * c) * pi;
+    const float e = __expf(l[c] - top);
+    s0 += e;
+    s1 += (float)c * e;
+    sd += (km - (float)c) * e;
   }
-  const float tail = __expf(l[K] - lse);
-  float dm, dv;
-  lik_mean_var<KIND>(a, dm, dv);
-  const float k = (float)K;
-  mean = m1 + tail * (dm + k);
-  var = m2 + tail * (2.f * k * dm + dv + dm * dm + k * k) - mean * mean;
+  const float ek = __expf(l[K] - top);
+  const float inv = 1.f / (s0 + ek);
+  const float tail = ek * inv;
+  mean = s1 * inv + tail * km;
+  const float d = sd * inv;
+  // (products ordered so that none overflows before the value does)
+  float acc = (tail * dm) * dq + (tail * d) * d;
+  for (int c = 0; c < K; ++c) {
+    const float dc = (float)c - mean;
+    acc += (__expf(l[c] - top) * inv * dc) * dc;
+  }
+  var = acc;
 }
 
 template <int KIND>

@@ -132,31 +132,50 @@ __device__ __forceinline__ void lik_elem(float t, const float* a, float& lp, flo
   }
 }
 
-// E[x|z] and Var[x|z] (TFP semantics; evaluate-time statistics, va:2665-2713)
+// E[x|z] = m and Var[x|z] / E[x|z] = q of the count distributions (TFP semantics).  The
+// variance travels as the factor q so that a zero-inflated or categorised variance below the
+// fp32 maximum is not lost to an overflow of its base distribution's.
+template <int KIND>
+__device__ __forceinline__ void lik_mean_dispersion(const float* a, float& m, float& q) {
+  static_assert(KIND == LK_POISSON || KIND == LK_NB, "count distributions only");
+  if constexpr (KIND == LK_POISSON) {
+    m = __expf(fminf(fmaxf(a[0], -10.f), 10.f));
+    q = 1.f;
+  } else {
+    const float ap = fmaxf(a[0], LOGIT_OF_TINY);
+    const float lr = fminf(fmaxf(a[1], -10.f), 10.f);
+    // r * p/(1-p) from ONE exponential: at the clip exp(ap) is the smallest normal float, the
+    // fast exponential returns 0 below it, and r would scale that loss up to 2.6e-34
+    m = __expf(lr + ap);
+    q = 1.f + __expf(ap);                // 1 / (1-p)
+  }
+}
+
+// E[x|z] and Var[x|z] (TFP semantics; evaluate-time statistics, va:2665-2713).  Every
+// variance is a product or sum of non-negative terms: the raw-moment forms of the reference
+// (zero_inflated.py:180-199, (1-pi)(v + m^2) - mean^2; Bernoulli, p (1 - p)) lose the value
+// in fp32 where the two moments agree to 2^-24 ("Stable forms").
 template <int KIND>
 __device__ __forceinline__ void lik_mean_var(const float* a, float& mean, float& var) {
   if constexpr (KIND == LK_CPOISSON) {
     // (the head has been normalised to the rate lambda * N by cpoisson_rate_rows)
     mean = a[0]; var = a[0];
   } else if constexpr (KIND == LK_BERNOULLI) {
-    const float pr = sigmoidf(a[0]);
-    mean = pr; var = pr * (1.f - pr);
-  } else if constexpr (KIND == LK_POISSON) {
-    const float lam = __expf(fminf(fmaxf(a[0], -10.f), 10.f));
-    mean = lam; var = lam;
-  } else if constexpr (KIND == LK_NB) {
-    const float ap = fmaxf(a[0], LOGIT_OF_TINY);
-    const float r = __expf(fminf(fmaxf(a[1], -10.f), 10.f));
-    mean = r * __expf(ap);               // r * p/(1-p)
-    var = mean * (1.f + __expf(ap));     // mean / (1-p)
+    mean = sigmoidf(a[0]);
+    var = mean * sigmoidf(-a[0]);
+  } else if constexpr (KIND == LK_POISSON || KIND == LK_NB) {
+    float q;
+    lik_mean_dispersion<KIND>(a, mean, q);
+    var = mean * q;
   } else {
-    float m, v;
-    if constexpr (KIND == LK_ZIP) lik_mean_var<LK_POISSON>(a + 1, m, v);
-    else lik_mean_var<LK_NB>(a + 1, m, v);
+    float m, q;
+    lik_mean_dispersion<(KIND == LK_ZIP ? LK_POISSON : LK_NB)>(a + 1, m, q);
     const float api = fmaxf(a[0], LOGIT_OF_TINY);
     const float omp = sigmoidf(-api);
+    const float pi = sigmoidf(api);
+    // (1-pi) (v + pi m^2) with v = m q
     mean = omp * m;
-    var = omp * (v + m * m) - mean * mean;
+    var = mean * (q + pi * m);
   }
 }
 #endif
