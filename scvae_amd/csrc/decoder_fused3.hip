@@ -151,12 +151,20 @@ __device__ __forceinline__ void split3_rn_pair(float x0, float x1, unsigned& p1,
 // One thread = one lane slot of a fragment, all three planes.  blockIdx.y: 0 = dA, 1 = dT.
 // (zero, zero16: the XCD-local accumulators of dd the training kernel is about to add into, as
 //  16-byte pieces -- cleared by this launch's threads instead of a memset launch of its own)
+// pack_ks >= 0 (the launches that go to the producer / consumer kernel at a width whose last
+// 32-wide block holds at most 8 live rows -- d4_packed): that block, k-step / h tile pack_ks with
+// h0 = 32 pack_ks, in the PACKED arrangement, its slot 8 a + h' standing for term a of row h0 + h':
+//   dA[pl][rb][pack_ks]   lane groups 0..2 (lane >> 4) all hold term pl of d[row, h0 + e], group 3
+//                         zeros: against a W fragment whose group a holds term a of W, one MFMA
+//                         sums over a as well
+//   dT[0][pack_ks][kg]    lane li < 24 holds term li >> 3 of d[row .., h0 + (li & 7)], the lanes
+//                         beyond zeros; the tile's places in planes 1 and 2 are zero and not read
 __global__ __launch_bounds__(256) void split3_hidden_kernel(const float* __restrict__ d, int R,
                                                             int H, int Rpad, int KP,
                                                             uint16_t* __restrict__ dA,
                                                             uint16_t* __restrict__ dT,
                                                             u32x4* __restrict__ zero,
-                                                            size_t zero16) {
+                                                            size_t zero16, int pack_ks) {
   const int slot = blockIdx.x * 256 + threadIdx.x;       // < Rpad * KP / 8
   for (size_t i = (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < zero16;
        i += (size_t)gridDim.x * gridDim.y * 256)
@@ -173,13 +181,32 @@ __global__ __launch_bounds__(256) void split3_hidden_kernel(const float* __restr
   if (blockIdx.y == 0) {
     const int rb = frag / ksp, ks = frag % ksp;
     const int row = 16 * rb + (lane & 15), k0 = 32 * ks + 8 * (lane >> 4);
+    if (ks == pack_ks) {
+      const bool live = (lane >> 4) < 3;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) split3_rn(value(row, k0 + e), t1[e], t2[e], t3[e]);
+      for (int e = 0; e < 8; ++e)
+        split3_rn(live ? value(row, 32 * ks + e) : 0.f, t1[e], t2[e], t3[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) split3_rn(value(row, k0 + e), t1[e], t2[e], t3[e]);
+    }
   } else {
     const int ht = frag / nb, kg = frag % nb;
     const int h = 32 * ht + (lane & 31), r0 = 16 * kg + 8 * (lane >> 5);
+    if (ht == pack_ks) {
+      const int a = (lane & 31) >> 3;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) split3_rn(value(r0 + e, h), t1[e], t2[e], t3[e]);
+      for (int e = 0; e < 8; ++e) {
+        unsigned s1, s2, s3;
+        split3_rn(a < 3 ? value(r0 + e, 32 * ht + (lane & 7)) : 0.f, s1, s2, s3);
+        t1[e] = a == 0 ? s1 : (a == 1 ? s2 : s3);
+        t2[e] = 0u;
+        t3[e] = 0u;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) split3_rn(value(r0 + e, h), t1[e], t2[e], t3[e]);
+    }
   }
   auto pack = [](const unsigned* t) {
     u32x4 v;
@@ -392,8 +419,29 @@ __device__ unsigned long long d4_prof[12 * 8];
 // the compiler drops its arithmetic), the consumers only add up the row sums.
 // IDX (decoder_head4_rows_kernel): the targets through the row index of a resident uint16 matrix,
 // fetched a tile ahead of the target prefetch that uses it (as in decoder_head3_kernel).
+// PACK (d4_packed: two to four contraction steps, the last with at most 8 live rows of [d | 1] --
+// H + 1 in 33..40, 65..72, 97..104): the last 32-wide block of h carries the three bf16 terms of
+// its live rows side by side, slot 8 a + h' = term a of row h0 + h' (h0 = 32 (KS1 - 1)), so that an
+// MFMA over the block sums over the term index of one operand as well and the block costs three
+// MFMAs per step, not nine, in all three products -- the same instructions, exact products and
+// fp32 accumulation:
+//   GEMM1  the W fragment's lane group a reads plane a of rows h0 .. h0 + 7 (group 3: the zero
+//          rows h0 + 8 ..), the fragments of d hold term b in groups 0..2 (split3_hidden_kernel):
+//          one MFMA per b;
+//   GEMM2  the block's consumer wave loads ONE fragment of d^T (row 8 a + h' = term a) and
+//          multiplies it with the three planes of G; the accumulator rows of the three terms of
+//          an h sit in one lane (registers i, i + 4, i + 8) and are added once, before dW is stored;
+//   GEMM3  that wave's W fragment: lane li reads plane li >> 3, row h0 + (li & 7) (the lanes from
+//          24: zero rows), times the three planes of G; the same three registers are added before
+//          the adds / stores of dd.
+// With six-term arithmetic the packed block still carries all nine terms (three MFMAs, cheaper
+// than six and no less accurate).
+__host__ __device__ constexpr bool d4_packed(int ks1, int H) {
+  return ks1 >= 2 && ks1 <= 4 && H + 1 - 32 * (ks1 - 1) >= 1 && H + 1 - 32 * (ks1 - 1) <= 8;
+}
 template <int KIND, int KS1, bool U16, int NPW, int BN_ = 0, bool DBP = false,
-          int G1 = (NPW == 4 ? 1 : D4_G1_EIGHT), int TERMS = 9, bool FWD = false>
+          int G1 = (NPW == 4 ? 1 : D4_G1_EIGHT), int TERMS = 9, bool FWD = false,
+          bool PACK = false>
 __global__ __launch_bounds__(d4_threads(NPW)) void decoder_head4_kernel(
     const uint16_t* __restrict__ dA, const uint16_t* __restrict__ dT, int R, int Rpad, int H,
     HeadParams hp, int F, Targets tg, int B, const float* __restrict__ gw, int inline_lgamma,
@@ -404,7 +452,7 @@ __global__ __launch_bounds__(d4_threads(NPW)) void decoder_head4_kernel(
 #include "decoder_head4_body.inc"
 }
 // the uint16 targets through a row index (all nine terms)
-template <int KIND, int KS1, int NPW, int BN_, bool DBP, int G1, bool FWD>
+template <int KIND, int KS1, int NPW, int BN_, bool DBP, int G1, bool FWD, bool PACK>
 __global__ __launch_bounds__(d4_threads(NPW)) void decoder_head4_rows_kernel(
     const uint16_t* __restrict__ dA, const uint16_t* __restrict__ dT, int R, int Rpad, int H,
     HeadParams hp, int F, Targets tg, int B, const float* __restrict__ gw, int inline_lgamma,
@@ -499,9 +547,11 @@ int decoder_fused3_train_kernel_name(int kind, int H, int rows, bool u16, char* 
   if (d3_schedule(P, H, rows) == 4) {
     const D4Config c = d4_config(P, H);
     const bool six = terms == 6 && c.ks1 <= 4 && c.bn == d3_bn(P) && !c.dbp;
-    return snprintf(out, n, "decoder_head4_kernel<%d, %d, %s, %d, %d, %s, %d, %d, false>", kind, c.ks1,
-                    u16 ? "true" : "false", c.npw, c.bn == d3_bn(P) ? 0 : c.bn,
-                    c.dbp ? "true" : "false", c.npw == 4 ? 1 : D4_G1_EIGHT, six ? 6 : 9);
+    const bool pack = c.bn == d3_bn(P) && !c.dbp && d4_packed(c.ks1, H);
+    return snprintf(out, n, "decoder_head4_kernel<%d, %d, %s, %d, %d, %s, %d, %d, false, %s>", kind,
+                    c.ks1, u16 ? "true" : "false", c.npw, c.bn == d3_bn(P) ? 0 : c.bn,
+                    c.dbp ? "true" : "false", c.npw == 4 ? 1 : D4_G1_EIGHT, six ? 6 : 9,
+                    pack ? "true" : "false");
   }
   return snprintf(out, n, "decoder_head3_kernel<%d, %d, %s, true, false, 0>", kind,
                   (d3_hp1(H) + 31) / 32, u16 ? "true" : "false");
@@ -574,13 +624,18 @@ struct D4Launch {
   bool fwd = false;      // the forward half alone (decoder_head4_kernel<..., FWD = true>)
   const int64_t* trows = nullptr;   // the uint16 targets through a row index (..._rows_kernel)
 };
-template <int KIND, int KS1, int NPW, int BN_, bool DBP = false, int TERMS = 9>
+template <int KIND, int KS1, int NPW, int BN_, bool DBP = false, int TERMS = 9, bool PACK = false>
 static int d4_launch_one(const D4Launch& a) {
   constexpr int G1 = NPW == 4 ? 1 : D4_G1_EIGHT;
+  // (the packed remainder block: an instantiation of its own, chosen here from H -- d4_packed;
+  //  decoder_fused3_launch asks split3_hidden_kernel for the packed planes by the same rule)
+  if constexpr (!PACK && KS1 >= 2 && KS1 <= 4 && BN_ == 0 && !DBP) {
+    if (d4_packed(KS1, a.H)) return d4_launch_one<KIND, KS1, NPW, BN_, DBP, TERMS, true>(a);
+  }
   // (six-term products: instantiated for the default strips up to four contraction steps, i.e.
   //  H <= 126; the wider geometries keep all nine terms)
   if constexpr (TERMS == 9 && KS1 <= 4 && BN_ == 0 && !DBP) {
-    if (a.terms == 6) return d4_launch_one<KIND, KS1, NPW, BN_, DBP, 6>(a);
+    if (a.terms == 6) return d4_launch_one<KIND, KS1, NPW, BN_, DBP, 6, PACK>(a);
   }
   const int tiles = (a.rows + D4_BM - 1) / D4_BM;
   const int rg_tiles = (tiles + a.row_groups - 1) / a.row_groups;
@@ -591,8 +646,8 @@ static int d4_launch_one(const D4Launch& a) {
         set_error("decoder_head4_kernel: a row index goes with uint16 targets and nine terms");
         return -1;
       }
-      auto rfn = a.fwd ? decoder_head4_rows_kernel<KIND, KS1, NPW, BN_, DBP, G1, true>
-                       : decoder_head4_rows_kernel<KIND, KS1, NPW, BN_, DBP, G1, false>;
+      auto rfn = a.fwd ? decoder_head4_rows_kernel<KIND, KS1, NPW, BN_, DBP, G1, true, PACK>
+                       : decoder_head4_rows_kernel<KIND, KS1, NPW, BN_, DBP, G1, false, PACK>;
       SCVAE_HIP(max_dynamic_lds(reinterpret_cast<const void*>(rfn), (int)a.lds));
       hipLaunchKernelGGL(rfn, dim3(a.strips, groups), dim3(d4_threads(NPW)), a.lds, a.s, a.dA,
                          a.dT, a.rows, a.Rpad, a.H, a.hp, a.F, a.t, a.B, a.gw, a.inline_lgamma,
@@ -608,8 +663,8 @@ static int d4_launch_one(const D4Launch& a) {
   }
   if constexpr (TERMS == 9) {
     if (a.fwd) {
-      auto ffn = a.t.u16 ? decoder_head4_kernel<KIND, KS1, true, NPW, BN_, DBP, G1, 9, true>
-                         : decoder_head4_kernel<KIND, KS1, false, NPW, BN_, DBP, G1, 9, true>;
+      auto ffn = a.t.u16 ? decoder_head4_kernel<KIND, KS1, true, NPW, BN_, DBP, G1, 9, true, PACK>
+                         : decoder_head4_kernel<KIND, KS1, false, NPW, BN_, DBP, G1, 9, true, PACK>;
       SCVAE_HIP(max_dynamic_lds(reinterpret_cast<const void*>(ffn), (int)a.lds));
       hipLaunchKernelGGL(ffn, dim3(a.strips, groups), dim3(d4_threads(NPW)), a.lds, a.s, a.dA,
                          a.dT, a.rows, a.Rpad, a.H, a.hp, a.F, a.t, a.B, a.gw, a.inline_lgamma,
@@ -617,8 +672,8 @@ static int d4_launch_one(const D4Launch& a) {
       return 0;
     }
   }
-  auto kfn = a.t.u16 ? decoder_head4_kernel<KIND, KS1, true, NPW, BN_, DBP, G1, TERMS>
-                     : decoder_head4_kernel<KIND, KS1, false, NPW, BN_, DBP, G1, TERMS>;
+  auto kfn = a.t.u16 ? decoder_head4_kernel<KIND, KS1, true, NPW, BN_, DBP, G1, TERMS, false, PACK>
+                     : decoder_head4_kernel<KIND, KS1, false, NPW, BN_, DBP, G1, TERMS, false, PACK>;
   SCVAE_HIP(max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)a.lds));
   hipLaunchKernelGGL(kfn, dim3(a.strips, groups), dim3(d4_threads(NPW)), a.lds, a.s, a.dA, a.dT,
                      a.rows, a.Rpad, a.H, a.hp, a.F, a.t, a.B, a.gw, a.inline_lgamma, a.ll_part,
@@ -718,12 +773,21 @@ int decoder_fused3_launch(hipStream_t s, bool train, int kind, const float* d, i
   const size_t acc_bytes = (size_t)8 * H * rows * sizeof(float);
   const bool clear_here = head4_train && (dd_mode & 1) && (acc_bytes & 15) == 0 &&
                           (reinterpret_cast<uintptr_t>(dd_part) & 15) == 0;
+  // (the planes' remainder block packed: only for the producer / consumer kernel, and only where
+  //  d4_launch_one picks its PACK instantiation; decoder_head3_kernel reads the plain layout)
+  const bool to_head4 = cp_pass == 0 && !drop &&
+                        (head4_train || (!train && wide));
+  int pack_ks = -1;
+  if (to_head4) {
+    const D4Config c = d4_config(P, H);
+    if (c.bn == d3_bn(P) && !c.dbp && d4_packed(c.ks1, H)) pack_ks = c.ks1 - 1;
+  }
   for (int j = 0; j < (drop ? P : 1); ++j) {
     hipLaunchKernelGGL(split3_hidden_kernel, dim3((Rpad * (KP / 8) + 255) / 256, train ? 2 : 1),
                        dim3(256), 0, s, drop ? drop->d[j] : d, rows, H, Rpad, KP,
                        dA + j * d3_set_elems(Rpad), dT + j * d3_set_elems(Rpad),
                        clear_here ? reinterpret_cast<u32x4*>(dd_part) : nullptr,
-                       clear_here ? acc_bytes / 16 : (size_t)0);
+                       clear_here ? acc_bytes / 16 : (size_t)0, pack_ks);
     SCVAE_LAUNCH_CHECK("split3_hidden_kernel");
     if (drop) {
       const int rc = dropout_mask_words(s, bits + (size_t)j * Rpad * 4, rows, Rpad, H, drop->keep,

@@ -160,6 +160,19 @@
         for (int sb = 0; sb < NSB; ++sb) acc1[j][sb] = f32x4m{0.f, 0.f, 0.f, 0.f};
       bf16x8 afr[2][P][NSB][3];
       auto load_w = [&](int ks, bf16x8 (&dst)[P][NSB][3]) {
+        if (PACK && ks == KS1 - 1) {
+          // (the packed block: lane group a = q reads plane a of rows h0 .. h0 + 7, group 3 the
+          //  zero rows h0 + 8 ..; one fragment per head and gene block, in slot 0)
+          const int trp = (q < 3 ? q * WPLANE : 8 * ROWB) + (i16 >> 2) * ROWB +
+                          2 * (gbase + 4 * (i16 & 3));
+#pragma unroll
+          for (int j = 0; j < P; ++j)
+#pragma unroll
+            for (int sb = 0; sb < NSB; ++sb)
+              dst[j][sb][0] = lds_tr8<ROWB>(Wl + (size_t)(j * 3) * WPLANE + trp + 32 * sb +
+                                            32 * ks * ROWB);
+          return;
+        }
 #pragma unroll
         for (int j = 0; j < P; ++j)
 #pragma unroll
@@ -173,6 +186,18 @@
 #pragma unroll
       for (int ks = 0; ks < KS1; ++ks) {
         if (ks + 1 < KS1) load_w(ks + 1, afr[(ks + 1) & 1]);
+        if (PACK && ks == KS1 - 1) {
+          // the W fragment holds the three terms side by side: one MFMA per term of d
+#pragma unroll
+          for (int b = 2; b >= 0; --b)
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+#pragma unroll
+              for (int sb = 0; sb < NSB; ++sb)
+                acc1[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    afr[ks & 1][j][sb][0], dfr[ks % DF][b], acc1[j][sb], 0, 0, 0);
+          continue;
+        }
         // small terms first; the accumulators (head x gene block) are independent chains
 #pragma unroll
         for (int a = 2; a >= 0; --a)
@@ -463,9 +488,19 @@
     if (dbg & 16) xcc = (blockIdx.x >> 3) & 7u;
   }
   const int n_ht3 = (H + 31) / 32, n_ht2 = DBP ? H / 32 : (H + 1 + 31) / 32;
+  static_assert(!PACK || (KS1 >= 2 && KS1 <= 4 && !DBP), "PACK: two to four steps, one h tile a wave");
+  // (PACK) the wave that owns the remainder tile runs the loop below in its packed form (PKW): a
+  // copy of the loop of its own, chosen once per wave, not a branch inside the loop
+  auto consume = [&](auto pkw_) __attribute__((always_inline)) {
+  constexpr bool PKW = decltype(pkw_)::value;
+  constexpr int NPL = PKW ? 1 : 3;          // planes of this wave's fragments of d^T and W
+  constexpr int NC = PKW ? 1 : 4;           // groups of eight h slots that hold rows of dd / dW
   // this wave's h tiles: ht, ht + 4, ... (NHT of them; one for H <= 126)
   const int g3a = li * ROWB + 16 * kh;                                               // G, GEMM3
-  const int g3b = (32 * ht + li) * ROWB + 16 * kh;                                   // W, GEMM3
+  // W, GEMM3 (PKW: lane li reads plane li >> 3, row h0 + (li & 7); from lane 24 the zero rows)
+  const int g3b = PKW ? (li < 24 ? (li >> 3) * WPLANE + (32 * ht + (li & 7)) * ROWB
+                                 : (32 * ht + 8 + (li & 7)) * ROWB) + 16 * kh
+                      : (32 * ht + li) * ROWB + 16 * kh;
   const int g2b = (8 * (q >> 1) + (i16 >> 2)) * ROWB + 2 * (16 * (q & 1) + 4 * (i16 & 3));  // G, GEMM2
   f32x16 accW[NHT][P][NGT];                 // dW tiles (h tile x gene tile) of every head
 #pragma unroll
@@ -479,16 +514,16 @@
   // GEMM2's d fragments (A[i = h][k = row]): one contiguous KiB per plane and 16-row k-step; the
   // two k-steps of (row tile, h tile) are requested while the wave works on the pair before
   constexpr int NA2 = NHT > 1 ? 2 : 1;
-  bf16x8 a2[NA2][2][3];
-  auto load_a2k = [&](int m0, int t, int ks, bf16x8 (&dst)[3]) {
+  bf16x8 a2[NA2][2][NPL];
+  auto load_a2k = [&](int m0, int t, int ks, bf16x8 (&dst)[NPL]) {
     // (h tile clamped to the planes' last: a wave without a tile t requests a valid one, unused
     //  -- no branch around the loads, at whose end the compiler would wait for them)
     const int htt = min(ht + 4 * t, ksp - 1);
     const uint16_t* tb = dT + ((size_t)htt * nb16 + m0 / 16 + ks) * 512 + lane * 8;
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) dst[pl] = global_b128(tb + pl * dplane);
+    for (int pl = 0; pl < NPL; ++pl) dst[pl] = global_b128(tb + pl * dplane);
   };
-  auto load_a2 = [&](int m0, int t, bf16x8 (&dst)[2][3]) {
+  auto load_a2 = [&](int m0, int t, bf16x8 (&dst)[2][NPL]) {
     load_a2k(m0, t, 0, dst[0]);
     load_a2k(m0, t, 1, dst[1]);
   };
@@ -516,7 +551,7 @@
     for (int t = 0; t < NHT; ++t) {
       if (ht + 4 * t < n_ht2 && !(dbg & 1)) {
         // ---- GEMM2: dW_j[h, gene] += sum_row d[row, h] G_j[row, gene] ----
-        bf16x8 (&a2t)[2][3] = a2[t % NA2];
+        bf16x8 (&a2t)[2][NPL] = a2[t % NA2];
         if (t == 0) {
           load_a2k(m0, 0, 1, a2[0][1]);
           d3_pin_loads();
@@ -540,10 +575,10 @@
           if (st + 1 < NST) load_2(st + 1, bf[(st + 1) & 1]);
           const int gt = st % NGT, j = (st / NGT) % P, ks = st / (NGT * P);
 #pragma unroll
-          for (int a = 2; a >= 0; --a)
+          for (int a = NPL - 1; a >= 0; --a)
 #pragma unroll
             for (int b = 2; b >= 0; --b)
-              if (TERMS == 9 || a + b < 3) accW[t][j][gt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2t[ks][a], bf[st & 1][b],
+              if (PKW || TERMS == 9 || a + b < 3) accW[t][j][gt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2t[ks][a], bf[st & 1][b],
                                                                        accW[t][j][gt], 0, 0, 0);
         }
       }
@@ -563,14 +598,15 @@
         f32x16 acc3;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc3[i] = 0.f;
-        bf16x8 af[2][3], bf[2][3];
-        auto load_3 = [&](int st, bf16x8 (&a)[3], bf16x8 (&b)[3]) {   // step = head * KS3 + k-step
+        bf16x8 af[2][3], bf[2][NPL];
+        auto load_3 = [&](int st, bf16x8 (&a)[3], bf16x8 (&b)[NPL]) {   // step = head * KS3 + k-step
           const int j = st / KS3, ks = st % KS3;
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
+          for (int pl = 0; pl < 3; ++pl)
             a[pl] = lds_b128(Gb + (size_t)(j * 3 + pl) * GPLANE + g3a + 32 * ks);
+#pragma unroll
+          for (int pl = 0; pl < NPL; ++pl)
             b[pl] = lds_b128(Wl + (size_t)(j * 3 + pl) * WPLANE + g3b + 128 * t * ROWB + 32 * ks);
-          }
         };
         load_3(0, af[0], bf[0]);
 #pragma unroll
@@ -579,9 +615,14 @@
 #pragma unroll
           for (int a = 2; a >= 0; --a)
 #pragma unroll
-            for (int b = 2; b >= 0; --b)
-              if (TERMS == 9 || a + b < 3) acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[st & 1][b], af[st & 1][a], acc3,
+            for (int b = NPL - 1; b >= 0; --b)
+              if (PKW || TERMS == 9 || a + b < 3) acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[st & 1][b], af[st & 1][a], acc3,
                                                              0, 0, 0);
+        }
+        if constexpr (PKW) {
+          // the three terms of row h0 + i + 4 kh: registers i, i + 4, i + 8 of this lane
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc3[i] += acc3[i + 4] + acc3[i + 8];
         }
         D4_STAMP(1);
         const int row = (dbg & 8) ? R : m0 + li;
@@ -592,7 +633,7 @@
             typedef __attribute__((address_space(1))) float gfloat;
             float* base = dd_part + ((size_t)xcc * H + 32 * htt + 4 * kh) * R + row;
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
+            for (int c = 0; c < NC; ++c)
 #pragma unroll
               for (int e = 0; e < 4; ++e)
                 if (32 * htt + 8 * c + 4 * kh + e < H)
@@ -605,7 +646,7 @@
           f32x4m* dst = reinterpret_cast<f32x4m*>(dd_part) +
                         ((size_t)blockIdx.x * HQ + 8 * htt + kh) * R + row;
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
+          for (int c = 0; c < NC; ++c) {
             if (4 * (8 * htt + 2 * c + kh) < H)
               __builtin_nontemporal_store(
                   f32x4m{acc3[4 * c], acc3[4 * c + 1], acc3[4 * c + 2], acc3[4 * c + 3]},
@@ -632,11 +673,21 @@
 #pragma unroll
           for (int j = 0; j < P; ++j)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
+            for (int i = 0; i < 4 * NC; ++i) {
               const int h = 32 * htt + (i & 3) + 8 * (i >> 2) + 4 * kh;
-              if (h <= H) grad_row(j, h)[c] = accW[t][j][gt][i];
+              // (PKW: the three terms of the row, accumulated side by side over the launch)
+              const float v = PKW ? accW[t][j][gt][i] + (accW[t][j][gt][i + 4] + accW[t][j][gt][i + 8])
+                                  : accW[t][j][gt][i];
+              if (h <= H) grad_row(j, h)[c] = v;
             }
         }
       }
     }
+  }
+  };   // consume
+  if constexpr (PACK) {
+    if (ht == KS1 - 1) consume(std::true_type{});
+    else consume(std::false_type{});
+  } else {
+    consume(std::false_type{});
   }

@@ -11,7 +11,7 @@ from collections import defaultdict
 
 def short(name):
     name = re.sub(r"\(.*$", "", name).replace("void ", "")
-    return name[:70]
+    return name[:80]
 
 
 def main():
