@@ -1,7 +1,9 @@
 """Edge shapes of the fused decoder-head kernel through the C ABI against an
 fp64 torch reference: row / gene counts around the 64-wide tiles, hidden sizes
 around the 32-wide MFMA tiles (incl. multiples of 32, where the ones-column of
-db lands in a tile of its own), queue overflow on dense counts, all kinds."""
+db lands in a tile of its own), queue overflow on dense counts, all kinds.
+The split terms of second order, far below these tolerances, are held by the
+single-product probes of ``test_gpu_head_probes.py``."""
 import ctypes
 import os
 import subprocess

@@ -7,6 +7,8 @@ bf16 terms of its rows side by side and costs three MFMAs per step instead of
 nine in GEMM1, GEMM2 and GEMM3.  The comparison and the tolerances are those
 of ``_run`` in ``tests/test_gpu_fused_decoder.py``: ``ll`` to 2e-5 of the
 largest value + 1e-4; ``dd``, ``dW``, ``db`` to 3e-5 of the largest element.
+The split terms of second order, far below these tolerances, are held by the
+single-product probes of ``test_gpu_head_probes.py``.
 
 Shapes: 200 rows (beyond 128 the producer / consumer kernel runs; seven
 32-row tiles, the last ragged), F = 196 for one and two heads and F = 90 for
