@@ -871,6 +871,50 @@ int scvae_tsne_gradient(const float* x, int64_t ldx, int64_t N, int64_t L, const
 int scvae_tsne_update(float* y, float* update, float* gains, const float* grad, int64_t N,
                       float momentum, float learning_rate, float min_gain, void* stream);
 
+/* ---- feature selection and example filters on a CSR count matrix
+ *      (scvae/data/processing.py:95-166 `select_features`: values.sum(axis=0) at :109 and
+ *      values.var(axis=0) at :115, 125, which the reference takes in fp32 as E[x^2] - E[x]^2;
+ *      :169-302 `filter_examples`; the values[:, indices] of :151 and values[filter_indices, :]
+ *      of :276 that SciPy does on the host).  indptr int64 [n_rows + 1], indices int32, values
+ *      fp32, all on the DEVICE; indices and values may be NULL only for a matrix without stored
+ *      entries.  `bad` is a DEVICE int32 word whose bits the kernels set and never clear:
+ *        bit 0 (1)   a value is not an integer in [0, 65535] (it is left out of the moments)
+ *        bit 1 (2)   a column index lies outside [0, F) (the entry is left out)
+ *        bit 2 (4)   a gene has 2^31 or more stored values != 0 (duplicate entries): its moments
+ *                    may have wrapped
+ *        bit 3 (8)   a row of the row list lies outside [0, n_rows) (taken as an empty row)
+ *        bit 4 (16)  out_indptr of scvae_csr_submatrix_fill is not the prefix sum of the counts
+ *                    (nothing is written outside an output row's own room)
+ *      Bad arguments return -1 and scvae_last_error() names them; nothing is launched then. ---- */
+/* sum[j] = sum_i x_ij and sum_sq[j] = sum_i x_ij^2 (uint64 [F]), nonzeros[j] = the number of
+ * stored values != 0 of gene j (int64 [F]): exact integers, N sum_sq - sum^2 is N^2 times the
+ * population variance.  1 <= n_rows <= 2^31 - 1 and 1 <= F <= 2^20, so that
+ * sum_sq <= 2^31 2^32 stays inside 64 bits.  Integer additions only: the same bits for every
+ * launch geometry and on every run.  No workspace: the workgroups accumulate slabs of 8192 genes
+ * in LDS and add them to the results (which the entry zeroes first) with one 64-bit integer
+ * atomic per result and touched gene. */
+int scvae_csr_feature_moments(const int64_t* indptr, const int32_t* indices, const float* values,
+                              int64_t n_rows, int64_t F, uint64_t* sum, uint64_t* sum_sq,
+                              int64_t* nonzeros, int32_t* bad, void* stream);
+/* The sub-matrix of the rows rows[0 .. n_out) (DEVICE int64; NULL: all rows in order, n_out =
+ * n_rows) and of the columns c with column_map[c] >= 0, which become column column_map[c]
+ * (DEVICE int32 [F]; NULL: all columns).  The map is expected to be monotone (a kept column's
+ * new index is its rank among the kept ones), so that sorted rows stay sorted; the entries of a
+ * row keep their order and explicitly stored zeros stay, as with SciPy's indexing.
+ * 1 <= n_rows, F <= 2^31 - 1, 0 <= n_out <= 2^31 - 1; entry offsets are int64.
+ * out_counts[o] (DEVICE int64 [n_out]) = the kept stored entries of output row o. */
+int scvae_csr_submatrix_count(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
+                              int64_t F, const int64_t* rows, int64_t n_out,
+                              const int32_t* column_map, int64_t* out_counts, int32_t* bad,
+                              void* stream);
+/* out_indptr (DEVICE int64 [n_out + 1]) = the exclusive prefix sum of out_counts, taken by the
+ * caller; out_indices / out_values [out_indptr[n_out]] receive the kept entries. */
+int scvae_csr_submatrix_fill(const int64_t* indptr, const int32_t* indices, const float* values,
+                             int64_t n_rows, int64_t F, const int64_t* rows, int64_t n_out,
+                             const int32_t* column_map, const int64_t* out_indptr,
+                             int32_t* out_indices, float* out_values, int32_t* bad,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

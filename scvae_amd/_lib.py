@@ -352,6 +352,15 @@ SIGNATURES = {
     "scvae_tsne_update": (c_int32, [
         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
         c_float, c_void_p]),
+    "scvae_csr_feature_moments": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_void_p]),
+    "scvae_csr_submatrix_count": (c_int32, [
+        c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+        c_void_p, c_void_p, c_void_p]),
+    "scvae_csr_submatrix_fill": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -116,10 +116,13 @@ def _model_arguments(arguments):
 def _load_data(data_set_file_or_name, data_format, data_directory,
                preprocessing_methods, noisy_preprocessing_methods,
                split_data_set, splitting_method, splitting_fraction,
-               binarise_values=False):
+               binarise_values=False, feature_selection=None,
+               example_filter=None):
     data_set = DataSet(
         data_set_file_or_name, data_format=data_format,
         directory=data_directory,
+        feature_selection=feature_selection,
+        example_filter=example_filter,
         preprocessing_methods=preprocessing_methods,
         noisy_preprocessing_methods=noisy_preprocessing_methods)
     if binarise_values:   # targets of the Bernoulli likelihood (cli.py:144-160)
@@ -136,6 +139,7 @@ def _load_data(data_set_file_or_name, data_format, data_directory,
 
 
 def train(data_set_file_or_name, data_format=None, data_directory=None,
+          feature_selection=None, example_filter=None,
           preprocessing_methods=None, noisy_preprocessing_methods=None,
           split_data_set=None, splitting_method=None, splitting_fraction=None,
           number_of_epochs=None, minibatch_size=None, learning_rate=None,
@@ -162,7 +166,8 @@ def train(data_set_file_or_name, data_format=None, data_directory=None,
         preprocessing_methods, noisy_preprocessing_methods, split_data_set,
         splitting_method, splitting_fraction,
         binarise_values=normalise_string(str(keyword_arguments.get(
-            "reconstruction_distribution"))) == "bernoulli")
+            "reconstruction_distribution"))) == "bernoulli",
+        feature_selection=feature_selection, example_filter=example_filter)
     training_set, validation_set, _ = subsets
 
     models_directory = build_directory_path(
@@ -204,6 +209,7 @@ def train(data_set_file_or_name, data_format=None, data_directory=None,
 
 
 def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
+             feature_selection=None, example_filter=None,
              preprocessing_methods=None, noisy_preprocessing_methods=None,
              split_data_set=None, splitting_method=None,
              splitting_fraction=None, minibatch_size=None, run_id=None,
@@ -322,7 +328,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
         preprocessing_methods, noisy_preprocessing_methods, split_data_set,
         splitting_method, splitting_fraction,
         binarise_values=normalise_string(str(keyword_arguments.get(
-            "reconstruction_distribution"))) == "bernoulli")
+            "reconstruction_distribution"))) == "bernoulli",
+        feature_selection=feature_selection, example_filter=example_filter)
     training_set, validation_set, test_set = subsets
     if split_data_set:
         kinds = {"training": training_set, "validation": validation_set,
@@ -674,7 +681,8 @@ def _parse_default(default):
     return default
 
 
-def main(arguments=None):
+def build_parser():
+    """The argument parser of ``main`` (``cli.py:668-1230``)."""
     parser = argparse.ArgumentParser(
         prog="scvae", description="Model single-cell transcript counts "
         "using deep learning (MI355X build of the training/evaluation path).",
@@ -707,6 +715,15 @@ def main(arguments=None):
         sub.add_argument("--data-directory", "-D", metavar="DIRECTORY",
                          default=_parse_default(dd["directory"]),
                          help="directory where data are placed or copied")
+        sub.add_argument("--feature-selection", "-F", metavar="SELECTION",
+                         nargs="+",
+                         default=_parse_default(dd["feature_selection"]),
+                         help="method for selecting features")
+        sub.add_argument("--example-filter", "-E", metavar="FILTER",
+                         nargs="+",
+                         default=_parse_default(dd["example_filter"]),
+                         help="method for filtering examples, optionally "
+                              "followed by parameters")
         sub.add_argument("--preprocessing-methods", "-p", metavar="METHOD",
                          nargs="+",
                          default=_parse_default(dd["preprocessing_methods"]),
@@ -961,7 +978,11 @@ def main(arguments=None):
         help="model versions to evaluate: end-of-training, best-model, "
              "early-stopping")
 
-    parsed = parser.parse_args(arguments)
+    return parser
+
+
+def main(arguments=None):
+    parsed = build_parser().parse_args(arguments)
     started = _start_data_parallel()
     try:
         import torch.distributed as dist

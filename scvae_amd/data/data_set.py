@@ -12,7 +12,8 @@ from time import time
 import numpy
 import scipy.sparse
 
-from scvae_amd.data.processing import build_preprocessor
+from scvae_amd.data.processing import (build_preprocessor, filter_examples,
+                                        select_features)
 from scvae_amd.data.sparse import SparseRowMatrix
 from scvae_amd.defaults import defaults
 from scvae_amd.utilities import normalise_string
@@ -50,8 +51,23 @@ class DataSet:
         self.specifications = specifications or {}
         self.directory = directory or defaults["data"]["directory"]
         self.features_mapped = features_mapped
-        self.feature_selection = feature_selection or []
-        self.example_filter = example_filter or []
+        # (data_set.py:306-331)
+        self.feature_selection = list(feature_selection or [])
+        self.feature_selection_method = None
+        self.feature_selection_parameters = None
+        if self.feature_selection:
+            self.feature_selection_method = self.feature_selection[0]
+            self.feature_selection_parameters = (
+                self.feature_selection[1:] or None)
+        self.example_filter = list(example_filter or [])
+        self.example_filter_method = None
+        self.example_filter_parameters = None
+        if self.example_filter:
+            self.example_filter_method = self.example_filter[0]
+            self.example_filter_parameters = self.example_filter[1:] or None
+        self.superset_labels = None
+        self.excluded_superset_classes = []
+        self._selected_and_filtered = False
         self.preprocessing_methods = preprocessing_methods or []
         # (data_set.py:362-375: a preprocessor applied anew every epoch of
         #  the training loop, va:960-976)
@@ -258,7 +274,25 @@ class DataSet:
                     labels=dictionary.get("labels"),
                     example_names=dictionary.get("example names"),
                     feature_names=dictionary.get("feature names"))
+        # (data_set.py:809-810)
+        if not self.feature_selection_parameters:
+            self.feature_selection_parameters = (
+                self.default_feature_parameters)
         self.preprocess()
+
+    @property
+    def default_feature_parameters(self):
+        """data_set.py:496-513."""
+        feature_selection_parameters = None
+        if self.feature_selection_method:
+            feature_selection = normalise_string(self.feature_selection_method)
+            if feature_selection == "keep_variances_above":
+                feature_selection_parameters = [0.5]
+            elif feature_selection == "keep_highest_variances":
+                if self.number_of_features is not None:
+                    feature_selection_parameters = [
+                        int(self.number_of_features / 2)]
+        return feature_selection_parameters
 
     def _sparse_cache_path(self):
         """``<directory>/<name>/preprocessed/<name>.sparse.h5``
@@ -275,6 +309,46 @@ class DataSet:
                 ", ".join(self.preprocessing_methods)))
             self.update(preprocessed_values=build_preprocessor(
                 self.preprocessing_methods)(self.values))
+        if ((self.feature_selection or self.example_filter)
+                and not self._selected_and_filtered):
+            self._select_and_filter()
+
+    def _select_and_filter(self):
+        """Feature selection on the original counts, applied to both versions
+        of the values, then the example filter (data_set.py:890-925, 952-982);
+        once, on the full set, before any split."""
+        values = self.values
+        preprocessed_values = self.preprocessed_values
+        updates = {}
+        if self.feature_selection:
+            values_dictionary, feature_names = select_features(
+                {"original": values, "preprocessed": preprocessed_values},
+                self.feature_names, method=self.feature_selection_method,
+                parameters=self.feature_selection_parameters)
+            values = values_dictionary["original"]
+            preprocessed_values = values_dictionary["preprocessed"]
+            updates["feature_names"] = feature_names
+            print()
+        if self.example_filter:
+            values_dictionary, example_names, labels, batch_indices = (
+                filter_examples(
+                    {"original": values, "preprocessed": preprocessed_values},
+                    self.example_names, method=self.example_filter_method,
+                    parameters=self.example_filter_parameters,
+                    labels=self.labels,
+                    excluded_classes=self.excluded_classes,
+                    superset_labels=self.superset_labels,
+                    excluded_superset_classes=self.excluded_superset_classes,
+                    batch_indices=self.batch_indices,
+                    count_sum=self.count_sum))
+            values = values_dictionary["original"]
+            preprocessed_values = values_dictionary["preprocessed"]
+            updates.update(example_names=example_names, labels=labels,
+                           batch_indices=batch_indices)
+            print()
+        self._selected_and_filtered = True
+        self.update(values=values, preprocessed_values=preprocessed_values,
+                    **updates)
 
     def binarise(self):
         """data_set.py:984-1024: values > 0.5 as the Bernoulli targets."""

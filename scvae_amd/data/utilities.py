@@ -31,9 +31,8 @@ def build_directory_path(base_directory, data_set, splitting_method=None,
     parts = []
     if getattr(data_set, "features_mapped", False):
         parts.append("features_mapped")
-    # (feature selection / example filters are not built -- SURVEY.md section 2
-    # OUT OF SCOPE -- but a data set object that carries them still gets the
-    # reference's directory name)
+    # (data_set.py:1285-1299: the method and its parameters, the defaults
+    # filled in by ``DataSet.load``)
     for kind in ("feature_selection", "example_filter"):
         method = getattr(data_set, kind + "_method", None)
         if method:
