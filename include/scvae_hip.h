@@ -660,6 +660,54 @@ int scvae_categorical_entropy_kl_fwd(const float* logits, float* y, float* kl_y_
 int scvae_categorical_entropy_kl_bwd(const float* y, const float* dy, const float* gate, float c,
                                      float* dlogits, int64_t B, int64_t K,
                                      const float* prior_logits, void* stream);
+/* The mixture ELBO (gm:3242-3410) in the two launches of a step.  ll, klz [K,S,B] (log p(t|z_k)
+ * and log q(z) - log p(z|y=k) per cluster, sample and cell), y [B,K], kl_y_cell [B]:
+ *   sums[0..2] = inv_gb * sum_b (sum_k y_bk mean_s ll, sum_k y_bk mean_s klz, kl_y_cell)
+ *   rec_cell (optional) [B] = sum_k y_bk mean_s ll
+ *   scalars[0..4] = share * (lower_bound, lower_bound_weighted, reconstruction_error,
+ *   kl_divergence_z, kl_divergence_y); scalars[7] += 1 when lower_bound is not finite (the
+ *   caller zeroes it; gm:1124-1127); scalars[5..6] are left as they are
+ *   gate[0] = 1 when kl_divergence_y > free_nats * H[p(y)] or free_nats == 0 (gm:3391-3398):
+ *   lower_bound_weighted = rec - w (kl_z + max(kl_y, free_nats * H[p(y)]))
+ * H[p(y)] = log K for the uniform prior (prior_logits NULL), the entropy of
+ * softmax(prior_logits) otherwise (gm:3256-3261).  inv_gb = 1 / cells of the global minibatch;
+ * share = this rank's part of it (1 on one GPU). */
+int scvae_mixture_elbo_fwd(const float* ll, const float* klz, const float* y,
+                           const float* kl_y_cell, int64_t K, int64_t S, int64_t B, float inv_gb,
+                           float w, float free_nats, float share, const float* prior_logits,
+                           float* sums, float* scalars, float* gate, float* rec_cell,
+                           void* stream);
+/* gradients of -lower_bound_weighted: gw[k,s,b] = -y_bk inv_gb / S (w.r.t. ll),
+ * gklz[k,s,b] = w y_bk inv_gb / S (w.r.t. klz), dy[b,k] = (w mean_s klz - mean_s ll) inv_gb */
+int scvae_mixture_elbo_bwd(const float* ll, const float* klz, const float* y, int64_t K,
+                           int64_t S, int64_t B, float w, float inv_gb, float* gw, float* gklz,
+                           float* dy, void* stream);
+/* gradient of w * max(mean_b KL(q(y|x_b) || p(y)), free_nats * H[p(y)]) w.r.t. the logits of a
+ * learned p(y) (gm:2794-2808, 3256-3261, 3391-3398): dprior[j] = c * sum_b (p_j - y_bj) with the
+ * gate on (c = w inv_gb), off_scale * free_nats * (-p_j (log p_j + H[p])) with it off
+ * (off_scale = w * share) */
+int scvae_prior_logits_bwd(const float* y, const float* prior_logits, const float* gate, float c,
+                           float off_scale, float free_nats, int64_t B, int64_t K, float* dprior,
+                           void* stream);
+/* The K passes of q(z|x,y=k) and p(x|z,y=k) (gm:2859-2922) stacked as groups of rows.
+ * out[g, c] = scale * sum_r a[g*R + r, c] for a [G*R, N] with row pitch lda: the one-hot rows of
+ * a weight gradient, the clusters' batch means q_z_means / q_z_variances (gm:2884-2887).
+ * workspace: scvae_group_col_sum_workspace_floats(G, N) floats. */
+int64_t scvae_group_col_sum_workspace_floats(int64_t G, int64_t N);
+int scvae_group_col_sum(const float* a, int64_t lda, int64_t R, int64_t G, int64_t N, float scale,
+                        float* out, float* workspace, void* stream);
+/* out[r, c] = sum_g w[r*ldw + g] * a[g*R + r, c] (w NULL: the plain sum over the groups):
+ * z_mean = sum_k y_k mean_k (gm:2895-2899) */
+int scvae_sum_groups(const float* a, const float* w, int64_t ldw, int64_t G, int64_t R, int64_t N,
+                     float* out, void* stream);
+/* out[k, b, :] = [relu](a0[b, :] + rows[k, :]): the first dense layer on concat(x, one_hot(k))
+ * of q(z|x,y=k) (gm:2936-3007) from one product with x and row F + k of the weights */
+int scvae_add_group_rows(const float* a0, const float* rows, float* out, int64_t K, int64_t B,
+                         int64_t N, int32_t relu, void* stream);
+/* p_z_means, p_z_variances [K, L] (gm:2879-2882): clip(Wpm + bpm) and softplus(clip(Wps + bps))
+ * with the clip at +-FLOAT32_MAX / 2 */
+int scvae_prior_stats(const float* Wpm, const float* bpm, const float* Wps, const float* bps,
+                      int64_t K, int64_t L, float* means, float* variances, void* stream);
 /* Importance-weighted bound (va:2717-2734 with log_reduce_exp, mu:129-137):
  * lower_bound = mean_{MC,B} log mean_IW exp(ll - KL), its KL-weighted twin, ENRE and KL into
  * scalars[0..3], and the backward in the same launch: gw[s*B + b] = d(-lower_bound_weighted) /

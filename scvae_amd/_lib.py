@@ -295,6 +295,29 @@ SIGNATURES = {
     "scvae_categorical_entropy_kl_bwd": (c_int32, [
         c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int64,
         c_void_p, c_void_p]),
+    "scvae_mixture_elbo_fwd": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+        c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_void_p]),
+    "scvae_mixture_elbo_bwd": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float,
+        c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scvae_prior_logits_bwd": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int64,
+        c_int64, c_void_p, c_void_p]),
+    "scvae_group_col_sum_workspace_floats": (c_int64, [c_int64, c_int64]),
+    "scvae_group_col_sum": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p,
+        c_void_p, c_void_p]),
+    "scvae_sum_groups": (c_int32, [
+        c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+        c_void_p]),
+    "scvae_add_group_rows": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
+        c_void_p]),
+    "scvae_prior_stats": (c_int32, [
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+        c_void_p, c_void_p]),
     "scvae_iw_logmeanexp": (c_int32, [
         c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_float,
         c_float, c_void_p, c_void_p, c_void_p]),

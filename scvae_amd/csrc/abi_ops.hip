@@ -327,6 +327,69 @@ int scvae_categorical_entropy_kl_bwd(const float* y, const float* dy, const floa
   return scvae::categorical_bwd_gated((hipStream_t)stream, y, dy, gate, c, dlogits, (int)B,
                                       (int)K, prior_logits);
 }
+int scvae_mixture_elbo_fwd(const float* ll, const float* klz, const float* y,
+                           const float* kl_y_cell, int64_t K, int64_t S, int64_t B, float inv_gb,
+                           float w, float free_nats, float share, const float* prior_logits,
+                           float* sums, float* scalars, float* gate, float* rec_cell,
+                           void* stream) {
+  SCVAE_ARG(ll && klz && y && kl_y_cell && sums && scalars && gate);
+  SCVAE_ARG(K > 0 && S > 0 && B > 0 && K <= INT32_MAX && S <= INT32_MAX && B <= INT32_MAX);
+  int rc = scvae::gmvae_elbo((hipStream_t)stream, ll, klz, y, kl_y_cell, (int)K, (int)S, (int)B,
+                             inv_gb, sums, rec_cell);
+  if (rc) return rc;
+  // (the uniform prior's threshold as a step forms it; recomputed on the device otherwise)
+  const float thr = free_nats * logf((float)K);
+  return scvae::gmvae_elbo_finish((hipStream_t)stream, sums, w, thr, free_nats != 0.f, share,
+                                  scalars, gate, prior_logits, (int)K, free_nats);
+}
+int scvae_mixture_elbo_bwd(const float* ll, const float* klz, const float* y, int64_t K,
+                           int64_t S, int64_t B, float w, float inv_gb, float* gw, float* gklz,
+                           float* dy, void* stream) {
+  SCVAE_ARG(ll && klz && y && gw && gklz && dy);
+  SCVAE_ARG(K > 0 && S > 0 && B >= 0 && K <= INT32_MAX && S <= INT32_MAX && B <= INT32_MAX);
+  return scvae::gmvae_elbo_bwd((hipStream_t)stream, ll, klz, y, nullptr, (int)K, (int)S, (int)B,
+                               w, inv_gb, gw, gklz, dy);
+}
+int scvae_prior_logits_bwd(const float* y, const float* prior_logits, const float* gate, float c,
+                           float off_scale, float free_nats, int64_t B, int64_t K, float* dprior,
+                           void* stream) {
+  SCVAE_ARG(y && prior_logits && gate && dprior && B >= 0 && K > 0 && B <= INT32_MAX &&
+            K <= INT32_MAX);
+  return scvae::prior_logits_bwd((hipStream_t)stream, y, prior_logits, gate, c, off_scale,
+                                 free_nats, (int)B, (int)K, dprior);
+}
+int64_t scvae_group_col_sum_workspace_floats(int64_t G, int64_t N) {
+  return G > 0 && N > 0 && G <= 65535 && N <= INT32_MAX
+             ? (int64_t)scvae::bn_partial_floats((int)G, (int)N)
+             : -1;
+}
+int scvae_group_col_sum(const float* a, int64_t lda, int64_t R, int64_t G, int64_t N, float scale,
+                        float* out, float* workspace, void* stream) {
+  SCVAE_ARG(a && out && workspace && R > 0 && G > 0 && N > 0 && lda >= N);
+  SCVAE_ARG(R <= INT32_MAX && G <= 65535 && N <= INT32_MAX && lda <= INT32_MAX);
+  return scvae::group_col_sum((hipStream_t)stream, a, (int)lda, (int)R, (int)G, (int)N, scale,
+                              out, workspace);
+}
+int scvae_sum_groups(const float* a, const float* w, int64_t ldw, int64_t G, int64_t R, int64_t N,
+                     float* out, void* stream) {
+  SCVAE_ARG(a && out && G > 0 && R >= 0 && N > 0 && (!w || ldw >= G));
+  SCVAE_ARG(G <= INT32_MAX && R <= INT32_MAX && N <= INT32_MAX && ldw <= INT32_MAX);
+  return scvae::sum_groups((hipStream_t)stream, a, w, (int)ldw, (int)G, (int)R, (int)N, out);
+}
+int scvae_add_group_rows(const float* a0, const float* rows, float* out, int64_t K, int64_t B,
+                         int64_t N, int32_t relu, void* stream) {
+  SCVAE_ARG(a0 && rows && out && K > 0 && B >= 0 && N > 0);
+  SCVAE_ARG(K <= INT32_MAX && B <= INT32_MAX && N <= INT32_MAX);
+  return scvae::add_group_rows((hipStream_t)stream, a0, rows, out, (int)K, (int)B, (int)N,
+                               relu ? 1 : 0);
+}
+int scvae_prior_stats(const float* Wpm, const float* bpm, const float* Wps, const float* bps,
+                      int64_t K, int64_t L, float* means, float* variances, void* stream) {
+  SCVAE_ARG(Wpm && bpm && Wps && bps && means && variances && K > 0 && L > 0 &&
+            K * L <= INT32_MAX - 255);
+  return scvae::prior_stats((hipStream_t)stream, Wpm, bpm, Wps, bps, (int)K, (int)L, means,
+                            variances);
+}
 int scvae_iw_logmeanexp(const float* ll, const float* kl_cell, int32_t kl_per_sample,
                         int32_t n_iw, int32_t n_mc, int64_t B, float kl_weight, float row_scale,
                         float* scalars, float* gw, void* stream) {

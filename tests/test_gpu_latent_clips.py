@@ -14,7 +14,9 @@ layers, so that no cell's gate can legitimately fall on either side.  The
 stand-alone cases call ``scvae_gauss_latent_fwd`` directly.
 
 The clip of the mean at +-FLOAT32_MAX_HALF needs activations of overflow
-scale and is not covered here.
+scale, which no step produces; its twin in the mixture's softplus-Gaussian
+pair is held stand-alone, with +-2e38 and +-inf pre-activations and the zeroed
+gradients, by ``test_pair_clip`` in tests/test_gpu_mixture_stage.py.
 """
 import ctypes
 import functools

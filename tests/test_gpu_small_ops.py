@@ -15,6 +15,7 @@ import torch
 from oracle import likelihoods as lk
 from oracle import models as om
 from _parity import close_elementwise, close_maxnorm, close_scalar
+import _mixture_oracle as mo
 
 pytestmark = pytest.mark.gpu
 
@@ -205,6 +206,13 @@ def test_softplus_gaussian_logprob_pair(cuda_device, K, S, B, L):
     want_kl = (om._normal_log_prob(zz, mean, sigma)
                - om._normal_log_prob(zz, pm, ps)).sum(dim=-1)
     ((zz * t["dz"]).sum() + (want_kl * t["gklz"]).sum()).backward()
+    # every element against fp64 on the fp32 inputs the device holds, each on the
+    # bound mo.pair derives from its own terms (dprior per cell, not summed)
+    held, _ = mo.pair({k: v.astype(np.float32) for k, v in arrays.items()}, K, S, B, L)
+    for name, got in (("z", z), ("klz", klz), ("qvar", qvar), ("dqm", dqm), ("dqs", dqs),
+                      ("dpr", dpr)):
+        mo.hold("{} [K {} S {} B {} L {}]".format(name, K, S, B, L), got, held[name])
+    # (and the per-tensor bounds these cases had before)
     _close(z, zz, 1e-6, "z")
     _close(klz, want_kl, 2e-5, "klz")
     _close(qvar, (sigma ** 2).reshape(K * B, L), 1e-6, "qvar")
@@ -248,6 +256,18 @@ def test_categorical_entropy_kl(cuda_device, B, K, prior):
     else:                # gm:3256-3258: kl(q_y || p_y)
         log_p = torch.log_softmax(torch.from_numpy(pl), dim=-1)
         want_kl = (yt * (log_y - log_p)).sum(dim=-1)
+    # every element against fp64 on the fp32 inputs the device holds, on the bounds
+    # mo.categorical_fwd / mo.categorical_bwd derive (the backward on the device's y)
+    l32, d32 = logits.astype(np.float32), dy.astype(np.float32)
+    p32 = None if pl is None else pl.astype(np.float32)
+    held, _ = mo.categorical_fwd(l32, p32)
+    tag = " [B {} K {} {}]".format(B, K, prior)
+    mo.hold("y" + tag, y, held["y"])
+    mo.hold("kl_y_cell" + tag, kl, held["kl"])
+    y_dev = y.cpu().numpy()
+    mo.hold("dlogits gate 1" + tag, dl, mo.categorical_bwd(y_dev, d32, 1.0, c, p32))
+    mo.hold("dlogits gate 0" + tag, dl0, mo.categorical_bwd(y_dev, d32, 0.0, c, p32))
+    # (and the per-tensor bounds these cases had before)
     _close(y, yt, 1e-6, "y")
     _close(kl, want_kl, 2e-5, "kl_y")
     ((yt * torch.from_numpy(dy)).sum() + c * want_kl.sum()).backward()
