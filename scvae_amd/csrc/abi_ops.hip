@@ -43,7 +43,7 @@ int64_t scvae_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 
 int scvae_loglik_fwd(int32_t kind, const float* t, const float* const* pre, const float* row_const,
                      float* ll, int64_t rows, int64_t cells, int64_t F, void* stream) {
-  SCVAE_ARG(pre && kind >= 0 && kind <= 3);
+  SCVAE_ARG(pre && ((kind >= 0 && kind <= 3) || kind == scvae::LK_BERNOULLI));
   scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
   for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = const_cast<float*>(pre[j]);
   return scvae::loglik_fwd((hipStream_t)stream, kind, t, (int)F, hp, (int)F, row_const, ll,
@@ -52,7 +52,7 @@ int scvae_loglik_fwd(int32_t kind, const float* t, const float* const* pre, cons
 int scvae_loglik_bwd(int32_t kind, const float* t, float* const* pre, const float* gw,
                      const float* row_const, float* ll, int64_t rows, int64_t cells, int64_t F,
                      void* stream) {
-  SCVAE_ARG(pre && kind >= 0 && kind <= 3);
+  SCVAE_ARG(pre && ((kind >= 0 && kind <= 3) || kind == scvae::LK_BERNOULLI));
   scvae::HeadPtrs hp = {{nullptr, nullptr, nullptr}};
   for (int j = 0; j < scvae::likelihood_heads(kind); ++j) hp.p[j] = pre[j];
   return scvae::loglik_bwd((hipStream_t)stream, kind, t, (int)F, hp, (int)F, gw, row_const, ll,

@@ -31,7 +31,9 @@ __global__ __launch_bounds__(256) void loglik_rows_kernel(const float* __restric
     for (int j = 0; j < P; ++j) a[j] = pre.p[j][(size_t)r * ldp + f];
     lik_elem<KIND, GRAD>(tv, a, lp, g);
     acc += lp;
-    if (row_const == nullptr) acc -= lgamma1p(tv);
+    // (the Bernoulli log-probability has no count term: du:194-204 hands targets to
+    //  tfp.distributions.Bernoulli, and t (t - 1) != 0 is outside its support either way)
+    if (KIND != LK_BERNOULLI && row_const == nullptr) acc -= lgamma1p(tv);
     if (GRAD) {
 #pragma unroll
       for (int j = 0; j < P; ++j) pre.p[j][(size_t)r * ldp + f] = g_up * g[j];
@@ -459,7 +461,7 @@ __global__ __launch_bounds__(256) void loglik_elementwise_kernel(const float* __
       const float tv = t[i];
       float lp;
       lik_elem<KIND, false>(tv, a, lp, g);
-      out[i] = lp - lgamma1p(tv);
+      out[i] = KIND == LK_BERNOULLI ? lp : lp - lgamma1p(tv);
     }
     if (mean != nullptr) {
       float m, v;
