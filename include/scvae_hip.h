@@ -649,6 +649,11 @@ int scvae_mvn_tril_logprob_pair_bwd(const float* qloc, const float* qscale, cons
                                     const float* eps, const float* dz, const float* gklz,
                                     float* dqloc, float* dqscale, float* dprior, int64_t K,
                                     int64_t S, int64_t B, int64_t L, void* stream);
+/* p(z|y=k) of the same pair for logging (gm:2879-2893): means [K, L] = Wpl[k] + bpl, variances
+ * [K, L] = diag(P P^T), covariances (optional) [K, L, L] = P P^T */
+int scvae_mvn_tril_prior_stats(const float* Wpl, const float* bpl, const float* Wps,
+                               const float* bps, int64_t K, int64_t L, float* means,
+                               float* variances, float* covariances, void* stream);
 /* q(y|x) = Categorical(logits) (gm:3050-3092): y = softmax(logits) [B, K] and
  * kl_y_cell[b] = KL(q(y|x_b) || p(y)): log K - H[q] for the uniform prior (prior_logits NULL,
  * gm:3242-3254), tfp kl_divergence against softmax(prior_logits) otherwise (gm:3256-3258) */

@@ -290,6 +290,8 @@ SIGNATURES = {
         c_void_p] * 11 + [c_int64] * 4 + [c_void_p]),
     "scvae_mvn_tril_logprob_pair_bwd": (c_int32, [
         c_void_p] * 12 + [c_int64] * 4 + [c_void_p]),
+    "scvae_mvn_tril_prior_stats": (c_int32, [
+        c_void_p] * 4 + [c_int64] * 2 + [c_void_p] * 4),
     "scvae_categorical_entropy_kl_fwd": (c_int32, [
         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "scvae_categorical_entropy_kl_bwd": (c_int32, [

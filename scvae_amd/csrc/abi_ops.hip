@@ -314,6 +314,13 @@ int scvae_mvn_tril_logprob_pair_bwd(const float* qloc, const float* qscale, cons
   return scvae::mvn_tril_bwd((hipStream_t)stream, qloc, qscale, Wpl, bpl, Wps, bps, eps, dz, gklz,
                              dqloc, dqscale, dprior, (int)K, (int)S, (int)B, (int)L);
 }
+int scvae_mvn_tril_prior_stats(const float* Wpl, const float* bpl, const float* Wps,
+                               const float* bps, int64_t K, int64_t L, float* means,
+                               float* variances, float* covariances, void* stream) {
+  SCVAE_ARG(K > 0 && K <= INT32_MAX && L > 0 && L <= 64);
+  return scvae::mvn_tril_prior_stats((hipStream_t)stream, Wpl, bpl, Wps, bps, (int)K, (int)L,
+                                     means, variances, covariances);
+}
 int scvae_categorical_entropy_kl_fwd(const float* logits, float* y, float* kl_y_cell, int64_t B,
                                      int64_t K, const float* prior_logits, void* stream) {
   SCVAE_ARG(logits && y && kl_y_cell && B >= 0 && K > 0 && B <= INT32_MAX);

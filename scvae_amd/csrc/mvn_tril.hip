@@ -260,8 +260,12 @@ __global__ __launch_bounds__(MVN_WAVES * WAVE) void mvn_tril_bwd_kernel(
     const int r = idx / L, c = idx - r * L;
     if (c <= r) {
       const int src = fill_src(r, c, L, T);
-      dqsc[kb * T + src] = GA[tri(r) + c] * scale_derivative(qsc[kb * T + src]);
-      dp[L + src] = GP[tri(r) + c] * scale_derivative(Wps[(size_t)k * T + src] + bps[src]);
+      // a clipped entry's gradient is selected, not multiplied: sum_s g / FLT_MIN on a clipped
+      // diagonal overflows once |sum_s g| passes 4, and inf * 0 is NaN
+      const float da = scale_derivative(qsc[kb * T + src]);
+      const float dpd = scale_derivative(Wps[(size_t)k * T + src] + bps[src]);
+      dqsc[kb * T + src] = da == 0.f ? 0.f : GA[tri(r) + c] * da;
+      dp[L + src] = dpd == 0.f ? 0.f : GP[tri(r) + c] * dpd;
     }
   }
 }
