@@ -968,6 +968,47 @@ int scvae_csr_submatrix_fill(const int64_t* indptr, const int32_t* indices, cons
                              int32_t* out_indices, float* out_values, int32_t* bad,
                              void* stream);
 
+/* ---- distributions of a resident matrix (scvae/analyses/subanalyses.py:119-146, 173-192: the
+ *      "Count distribution" and "Count sum distribution" of `analyse_distributions`;
+ *      scvae/analyses/figures/histograms.py:142-179 `plot_histogram`, whose numpy.histogram with
+ *      bins="auto" takes numpy.percentile twice; all of which the reference does on the host on a
+ *      flattened copy).  x [rows, F] fp32 on the DEVICE, row pitch ldx >= F in elements, unit
+ *      column stride, 4-byte aligned, element offsets int64; columns F .. ldx - 1 are never read;
+ *      16-byte loads wherever a row's alignment allows.  rows >= 1, rows * ldx <= 2^60;
+ *      1 <= F <= 2^31 - 1, and up to 2^40 for a flat array (rows = 1).  shift != 0: the element is
+ *      fl32(x + 1.0f), the `series += 1` of histograms.py:160.  Bad arguments return -1 and
+ *      scvae_last_error() names them; nothing is launched then. ---- */
+/* counts[i] (DEVICE int64 [n_bins]) += the number of elements of bin i over the non-decreasing
+ * DEVICE edges e[0 .. n_bins] (fp32; fp64 with bit 0 of `flags`): an element with
+ * e[0] <= x <= e[n_bins] belongs to the largest i <= n_bins - 1 with e[i] <= x (the last bin is
+ * closed on the right), compared in fp64 -- numpy.histogram's counts for the edges of
+ * numpy.histogram_bin_edges.  outside[0 .. 2] (DEVICE int64) += the elements below e[0], above
+ * e[n_bins], and NaN.  Nothing is zeroed: calls accumulate.  1 <= n_bins <= 2^20, in slabs of 8192
+ * bins (one more pass over x per slab; 64 KiB of LDS for a full slab of fp32 edges, 96 KiB of fp64).  Integer additions only:
+ * the same bits for every launch geometry and on every run.  Bit 1 of `flags` (measurements
+ * only) turns the aggregation of equal bins inside a wave off; the counts are the same. */
+int scvae_histogram_accumulate(const float* x, int64_t ldx, int64_t rows, int64_t F, int32_t shift,
+                               const void* edges, int32_t flags, int64_t n_bins, int64_t* counts,
+                               int64_t* outside, void* stream);
+/* values[k] (DEVICE fp32 [n_ranks]) = the ranks[k]-th smallest element (HOST int64, zero-based,
+ * 0 <= ranks[k] < rows * F, 1 <= n_ranks <= 4), exact, by a radix select in three passes over x
+ * (no sort, no copy; what numpy.percentile partitions a copy for).  -0.0 orders before +0.0; NaN
+ * elements order last, as in numpy.sort: a rank past the last other element gives NaN.
+ * extremes[0 .. 1] (DEVICE fp32) = minimum and maximum of the elements that are not NaN (NaN
+ * where there is none); counts[0 .. 1] (DEVICE int64) = rows * F and the number of NaN.  With
+ * `shift` every returned value is fl32(v + 1.0f) of the unshifted one (x -> fl32(x + 1) is
+ * non-decreasing).  rows * F <= 2^42.  Integer sums only: identical on every run. */
+int64_t scvae_order_statistics_workspace_bytes(void);
+int scvae_order_statistics(const float* x, int64_t ldx, int64_t rows, int64_t F, int32_t shift,
+                           const int64_t* ranks, int32_t n_ranks, float* values, float* extremes,
+                           int64_t* counts, void* workspace, int64_t workspace_bytes,
+                           void* stream);
+/* out[r] (DEVICE fp32 [rows]) = the fp64 sum of row r in one fixed order, rounded once to fp32
+ * (the reference's values.sum(axis=1) adds in fp32, data_set.py `count_sum`: a deliberate
+ * difference).  One workgroup per row: a flat array of 2^40 elements is allowed and slow. */
+int scvae_row_sums_f64(const float* x, int64_t ldx, int64_t rows, int64_t F, int32_t shift,
+                       float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -386,6 +386,15 @@ SIGNATURES = {
     "scvae_csr_submatrix_fill": (c_int32, [
         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scvae_histogram_accumulate": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int32,
+        c_int64, c_void_p, c_void_p, c_void_p]),
+    "scvae_order_statistics_workspace_bytes": (c_int64, []),
+    "scvae_order_statistics": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_int32, POINTER(c_int64),
+        c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "scvae_row_sums_f64": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

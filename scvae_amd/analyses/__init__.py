@@ -5,9 +5,10 @@ the summary statistics of the evaluation set and of its reconstruction, the
 metrics table of ``analyse_results`` (``scvae/analyses/metrics/summary.py``),
 the PCA of its "Decompositions"
 (``scvae/analyses/decomposition/decomposition.py``), and the t-SNE map of its
-"latent space" (``scvae/analyses/subanalyses.py:595-673``).  The ``analyse``
-command, the metrics files, plots and the other decomposition methods are not
-part of this build."""
+"latent space" (``scvae/analyses/subanalyses.py:595-673``), and the
+histograms of its "Distributions" (``scvae/analyses/subanalyses.py:50-291``)
+as tables.  The ``analyse`` command, the metrics files, plots and the other
+decomposition methods are not part of this build."""
 from scvae_amd.analyses.prediction import (  # noqa: F401
     PREDICTION_METHODS, PredictionSpecifications, predict_labels,
     map_cluster_ids_to_label_ids)
@@ -21,3 +22,5 @@ from scvae_amd.analyses.decomposition import (  # noqa: F401
     DevicePCA, decompose)
 from scvae_amd.analyses.tsne import (  # noqa: F401
     DeviceTSNE, decompose_latent)
+from scvae_amd.analyses.distributions import (  # noqa: F401
+    distribution_histograms, histogram, order_statistics, percentile)

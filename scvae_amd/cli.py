@@ -219,8 +219,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              silhouette_score=False, silhouette_space="latent",
              summary_statistics=False, analysis_level=None,
              decompositions=False, decomposition_methods=None,
-             latent_space=False, analyses_directory=None,
-             **keyword_arguments):
+             latent_space=False, distributions=False,
+             analyses_directory=None, **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
 
     ``decompositions`` (not in the reference's ``evaluate``, which leaves it
@@ -242,6 +242,15 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     reference fits the Barnes-Hut approximation on the host.  The coordinates
     go to tab-separated files under ``analyses_directory``.  With several
     ranks only rank 0 fits and writes (not tested on more than one GPU).
+
+    ``distributions`` (not in the reference's ``evaluate``, which leaves it
+    to ``analyse_results``): after the evaluation of each model version the
+    histograms of its "Distributions" (``analyses.py:1226-1235``,
+    ``subanalyses.py:50-291``) of the reconstructed set -- counts, counts
+    shifted by one, and count sums -- computed on the GPU on the
+    reconstruction where it lies (``analyses/distributions.py``); with
+    ``analysis_level="extensive"`` also those of the evaluation set.  Each
+    goes to a tab-separated file under ``analyses_directory``.
 
     ``summary_statistics`` (not in the reference's ``evaluate``, which leaves
     it to ``analyse_results``): after the evaluation of each model version
@@ -274,8 +283,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     if silhouette_score and silhouette_space not in ("latent", "counts"):
         raise ValueError("Silhouette space `{}` not found.".format(
             silhouette_space))
-    summary_level = decomposition_level = None
-    if summary_statistics or decompositions:
+    summary_level = decomposition_level = distributions_level = None
+    if summary_statistics or decompositions or distributions:
         if analysis_level is None:
             analysis_level = defaults["analyses"]["analysis_level"]
         analysis_level = normalise_string(str(analysis_level))
@@ -287,6 +296,10 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             summary_level = level
         if decompositions:
             decomposition_level = level
+        if distributions:
+            distributions_level = level
+    if distributions_level and analyses_directory is None:
+        analyses_directory = defaults["analyses"]["directory"]
     if decomposition_level or latent_space:
         from scvae_amd.analyses.decomposition import method_name
         if decomposition_methods is None:
@@ -411,7 +424,9 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
                else {}),
             **({"decompositions": decomposition_level}
                if decomposition_level and "PCA" in decomposition_methods
-               else {}))
+               else {}),
+            **({"distributions": distributions_level}
+               if distributions_level else {}))
         if summary_level:   # analyses.py:873-899, 1040-1041
             _print_summary_statistics(results[model_version][1])
         print()
@@ -426,7 +441,7 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             results[model_version] = (
                 results[model_version], sample_reconstruction_set)
             print()
-        if decomposition_level or latent_space:
+        if decomposition_level or latent_space or distributions_level:
             evaluation_results = (results[model_version][0] if sample_size
                                   else results[model_version])
             version_directory = _decompositions_directory(
@@ -444,6 +459,9 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             _report_latent_space(
                 evaluation_results[2], decomposition_methods,
                 version_directory)
+        if distributions_level:   # analyses.py:1226-1235
+            _report_distributions(
+                evaluation_results[1], evaluation_set, version_directory)
         if prediction_specifications is not None:   # cli.py:509-543
             _predict(model, results[model_version], prediction_training_set,
                      prediction_specifications, minibatch_size, run_id,
@@ -560,6 +578,33 @@ def _report_decompositions(reconstructed_set, methods, sampled_set,
             _write_coordinates(
                 os.path.join(directory, name, "pca-sampled.tsv"), sampled_set,
                 fit["model"].transform(sampled_set.values))
+
+
+def _report_distributions(reconstructed_set, evaluation_set, directory):
+    """The lines of ``analyse_distributions`` (``subanalyses.py:64-72,
+    145-146, 191-192, 291``) for the histograms ``model.evaluate`` attached
+    to the reconstructed set, three per set, and one tab-separated file for
+    each, ``histograms/<figure name>.tsv``.  With several ranks only rank 0
+    has them: the others print and write nothing."""
+    from scvae_amd.analyses.distributions import write_histogram
+    histograms = getattr(reconstructed_set, "distributions", None)
+    if histograms is None:
+        return
+    set_titles = ["reconstructed {} set".format(evaluation_set.kind),
+                  "{} set".format(evaluation_set.kind)]
+    for first in range(0, len(histograms), 3):
+        counts, log_counts, count_sum = histograms[first:first + 3]
+        print("Plotting distributions for {}.".format(
+            set_titles[first // 3]))
+        print("    Count distribution plotted and saved ({}).".format(
+            format_duration(counts["duration"] + log_counts["duration"])))
+        print("    Count sum distribution plotted and saved ({}).".format(
+            format_duration(count_sum["duration"])))
+        print()
+        for histogram in (counts, log_counts, count_sum):
+            write_histogram(
+                os.path.join(directory, "histograms",
+                             histogram["name"] + ".tsv"), histogram)
 
 
 def _report_latent_space(latent_sets, methods, directory):
@@ -948,7 +993,8 @@ def build_parser():
              "which adds the rows of the differences and of the log-ratios "
              "between the reconstructed and the evaluation set; with "
              "--decompositions: extensive adds the reconstructions in the "
-             "space of the originals")
+             "space of the originals; with --distributions: extensive adds "
+             "the histograms of the evaluation set")
     parser_evaluate.add_argument(
         "--decompositions", action="store_true", default=False,
         help="(this build) after the evaluation of each model version, fit "
@@ -957,6 +1003,14 @@ def build_parser():
              "where the reference fits an incremental one), print its "
              "explained-variance ratios and write the coordinates of every "
              "example to a tab-separated file under --analyses-directory")
+    parser_evaluate.add_argument(
+        "--distributions", action="store_true", default=False,
+        help="(this build) after the evaluation of each model version, the "
+             "histograms of the reconstructed set (counts, counts shifted "
+             "by one, count sums), exact over NumPy's bin edges, on the GPU "
+             "before the reconstruction leaves it, each written as a "
+             "tab-separated table under --analyses-directory; with "
+             "--analysis-level extensive also those of the evaluation set")
     parser_evaluate.add_argument(
         "--decomposition-methods", metavar="METHOD", nargs="+",
         default=_parse_default(defaults["analyses"]["decomposition_method"]),

@@ -1338,6 +1338,23 @@ class ModelBase:
             raise ValueError(
                 "Decompositions need the reconstructed set: "
                 "\"reconstructed\" must be in the output versions.")
+        # (not in the reference's signature) the histograms of
+        # analyse_results' "Distributions" (analyses.py:1226-1235) as tables,
+        # attached to the returned reconstructed set as ``distributions``;
+        # "extensive" adds those of the evaluation set
+        distributions_level = kwargs.get("distributions")
+        if distributions_level is None or distributions_level is False:
+            distributions_level = None
+        elif distributions_level is True:
+            distributions_level = "normal"
+        elif distributions_level not in ("normal", "extensive"):
+            raise ValueError(
+                "Distributions `{}` not found: None, False, True, "
+                "\"normal\" or \"extensive\".".format(distributions_level))
+        if distributions_level and "reconstructed" not in output_versions:
+            raise ValueError(
+                "Distributions need the reconstructed set: "
+                "\"reconstructed\" must be in the output versions.")
 
         minibatch_size = self._training_minibatch_size(
             minibatch_size, "evaluation")
@@ -1469,6 +1486,19 @@ class ModelBase:
                     evaluation_decomposition(
                         densify(t_eval), projected=outputs["p_x_mean"]))
 
+        distributions = None
+        if distributions_level and master:
+            # over p_x_mean where it lies, before its copy to the host; the
+            # evaluation set is what the likelihood saw (t_eval)
+            from scvae_amd.analyses.distributions import (
+                evaluation_distributions)
+            distributions_time_start = time()
+            distributions = evaluation_distributions(
+                t_eval, outputs["p_x_mean"], kind=evaluation_set.kind,
+                extensive=distributions_level == "extensive",
+                preprocessed=bool(evaluation_set.preprocessing_methods))
+            distributions_duration = time() - distributions_time_start
+
         output_sets = [None] * len(output_versions)
         if "transformed" in output_versions:
             # (va:2135-2158: the binarised / noisily preprocessed values the
@@ -1502,6 +1532,12 @@ class ModelBase:
                 reconstructed_set.summary_statistics = summary_rows
                 reconstructed_set.summary_statistics_duration = (
                     summary_duration)
+            if distributions is not None:
+                reconstructed_set = output_sets[
+                    output_versions.index("reconstructed")]
+                reconstructed_set.distributions = distributions
+                reconstructed_set.distributions_duration = (
+                    distributions_duration)
             for name, decomposition in decompositions.items():
                 setattr(output_sets[output_versions.index("reconstructed")],
                         name, decomposition)
