@@ -1009,6 +1009,38 @@ int scvae_order_statistics(const float* x, int64_t ldx, int64_t rows, int64_t F,
 int scvae_row_sums_f64(const float* x, int64_t ldx, int64_t rows, int64_t F, int32_t shift,
                        float* out, void* stream);
 
+/* ---- pairwise distances between the rows of a resident matrix
+ *      (scvae/analyses/figures/matrices.py:124-130: sklearn.metrics.pairwise_distances(values,
+ *      metric=...) of `plot_matrix`, called four times per set by `analyse_matrices`,
+ *      scvae/analyses/subanalyses.py:294-468, with up to 10 000 sampled rows on the host).
+ *      x [total_rows, F] fp32 on the DEVICE, row pitch ldx >= F in elements, unit column stride,
+ *      4-byte aligned; columns F .. ldx - 1 are never read.  rows (DEVICE int64 [n], or NULL for the
+ *      rows 0 .. n - 1) are the positions of the sample in x in the wanted order, duplicates
+ *      allowed; the rows are read in place, no copy of n x F is made.  A position outside
+ *      [0, total_rows) is clamped into it by the kernel, so that nothing outside x is read: the
+ *      caller validates the index.  out [n, n] fp32 on the DEVICE, row pitch ldo >= n.
+ *      1 <= n <= 2^16, 1 <= F <= 2^20.
+ *
+ *      g_ij = sum_k x_ik x_jk on v_mfma_f64_16x16x4_f64: exact products of the fp32 values, fp64
+ *      additions in one fixed order that is the same for every i, j (K is not split; no atomics).
+ *      Only the 128 x 128 tiles on or above the diagonal are computed and d_ji is written from the
+ *      value of d_ij; g_ii comes from the diagonal tiles of the same kernel in a first pass
+ *      (workspace: fp64 [n]).  The metric is applied in fp64 and rounded to fp32 once:
+ *        SCVAE_DISTANCE_EUCLIDEAN  sqrt(max(0, g_ii + g_jj - 2 g_ij))
+ *        SCVAE_DISTANCE_COSINE     1 - g_ij / sqrt(g_ii g_jj) clipped to [0, 2]; a row of zero
+ *                                  norm has similarity 0 (distance 1) to every other row
+ *      Identical bits on every run, d_ij == d_ji bit for bit, d_ii == 0, and rows with identical
+ *      values at exactly 0 in both metrics (scikit-learn's expanded fp32 form leaves ~2e-7).  A
+ *      value that is not finite gives NaN in its row and column (not on the diagonal).  Bad
+ *      arguments return -1 and scvae_last_error() names them; nothing is launched then. ---- */
+#define SCVAE_DISTANCE_EUCLIDEAN 0
+#define SCVAE_DISTANCE_COSINE 1
+int64_t scvae_pairwise_distances_workspace_bytes(int64_t n, int64_t F);
+int scvae_pairwise_distances(const float* x, int64_t ldx, int64_t total_rows, int64_t F,
+                             const int64_t* rows, int64_t n, int32_t metric, float* out,
+                             int64_t ldo, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -395,6 +395,10 @@ SIGNATURES = {
         c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "scvae_row_sums_f64": (c_int32, [
         c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    "scvae_pairwise_distances_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "scvae_pairwise_distances": (c_int32, [
+        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32,
+        c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -219,7 +219,7 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
              silhouette_score=False, silhouette_space="latent",
              summary_statistics=False, analysis_level=None,
              decompositions=False, decomposition_methods=None,
-             latent_space=False, distributions=False,
+             latent_space=False, distributions=False, distances=False,
              analyses_directory=None, **keyword_arguments):
     """Evaluate model on data set (``cli.py:267-566``).
 
@@ -251,6 +251,17 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
     reconstruction where it lies (``analyses/distributions.py``); with
     ``analysis_level="extensive"`` also those of the evaluation set.  Each
     goes to a tab-separated file under ``analyses_directory``.
+
+    ``distances`` (not in the reference's ``evaluate``, which leaves it to
+    ``analyse_results``): after the evaluation of each model version the
+    pairwise distance matrices of its "Distances" (``analyses.py:1351-1362``,
+    ``subanalyses.py:294-468``) of the reconstructed set and of the ``z``
+    latent values -- Euclidean and cosine, sorted by labels (where the set
+    has labels) and by hierarchical clustering, over 10 000 and 1 000
+    sampled examples at most -- computed on the GPU on the reconstruction
+    where it lies (``analyses/distances.py``).  Each goes to a ``.npy`` file
+    with a ``.tsv`` table of its examples under ``analyses_directory``; a
+    matrix of 10 000 examples is 400 MB.
 
     ``summary_statistics`` (not in the reference's ``evaluate``, which leaves
     it to ``analyse_results``): after the evaluation of each model version
@@ -298,7 +309,7 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             decomposition_level = level
         if distributions:
             distributions_level = level
-    if distributions_level and analyses_directory is None:
+    if (distributions_level or distances) and analyses_directory is None:
         analyses_directory = defaults["analyses"]["directory"]
     if decomposition_level or latent_space:
         from scvae_amd.analyses.decomposition import method_name
@@ -426,7 +437,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
                if decomposition_level and "PCA" in decomposition_methods
                else {}),
             **({"distributions": distributions_level}
-               if distributions_level else {}))
+               if distributions_level else {}),
+            **({"distances": True} if distances else {}))
         if summary_level:   # analyses.py:873-899, 1040-1041
             _print_summary_statistics(results[model_version][1])
         print()
@@ -441,7 +453,8 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
             results[model_version] = (
                 results[model_version], sample_reconstruction_set)
             print()
-        if decomposition_level or latent_space or distributions_level:
+        if (decomposition_level or latent_space or distributions_level
+                or distances):
             evaluation_results = (results[model_version][0] if sample_size
                                   else results[model_version])
             version_directory = _decompositions_directory(
@@ -462,6 +475,10 @@ def evaluate(data_set_file_or_name, data_format=None, data_directory=None,
         if distributions_level:   # analyses.py:1226-1235
             _report_distributions(
                 evaluation_results[1], evaluation_set, version_directory)
+        if distances:   # analyses.py:1351-1362
+            _report_distances(
+                evaluation_results[1], evaluation_results[2],
+                version_directory)
         if prediction_specifications is not None:   # cli.py:509-543
             _predict(model, results[model_version], prediction_training_set,
                      prediction_specifications, minibatch_size, run_id,
@@ -605,6 +622,36 @@ def _report_distributions(reconstructed_set, evaluation_set, directory):
             write_histogram(
                 os.path.join(directory, "histograms",
                              histogram["name"] + ".tsv"), histogram)
+
+
+def _report_distances(reconstructed_set, latent_sets, directory):
+    """The lines of ``analyse_matrices(..., plot_distances=True)``
+    (``subanalyses.py:369-372, 437-468``) for the distance matrices
+    ``model.evaluate`` attached to the reconstructed set and to the latent
+    set ``z``, and two files for each under ``distances/``: the matrix in
+    plotted order as ``<figure name>.npy`` and the table of its examples as
+    ``<figure name>.tsv``.  With several ranks only rank 0 has them: the
+    others print and write nothing."""
+    from scvae_amd.analyses.distances import write_distances
+    for data_set in (reconstructed_set, (latent_sets or {}).get("z")):
+        matrices = getattr(data_set, "distance_matrices", None)
+        if matrices is None:
+            continue
+        print("Plotting pairwise distances in {} space.".format(
+            data_set.version))
+        for matrix in matrices:
+            write_distances(os.path.join(directory, "distances"), matrix)
+            print("    " + " ".join(s for s in [
+                "{} distances in {} space".format(
+                    matrix["metric"].capitalize(), data_set.version),
+                ("for {} randomly sampled examples".format(
+                    matrix["sample_size"]) if matrix["sample_size"] else ""),
+                "sorted using {}".format(
+                    matrix["sorting_method"].replace("_", " ")),
+                "plotted and saved",
+                "({})".format(format_duration(matrix["duration"]))
+            ] if s) + ".")
+        print()
 
 
 def _report_latent_space(latent_sets, methods, directory):
@@ -1011,6 +1058,16 @@ def build_parser():
              "before the reconstruction leaves it, each written as a "
              "tab-separated table under --analyses-directory; with "
              "--analysis-level extensive also those of the evaluation set")
+    parser_evaluate.add_argument(
+        "--distances", action="store_true", default=False,
+        help="(this build) after the evaluation of each model version, the "
+             "pairwise distance matrices of the reconstructed set and of the "
+             "z latent values (Euclidean and cosine; sorted by labels, where "
+             "there are labels, over at most 10 000 sampled examples, and by "
+             "hierarchical clustering over at most 1 000), on the GPU before "
+             "the reconstruction leaves it, each written as a .npy matrix "
+             "with a .tsv table of its examples under --analyses-directory; "
+             "a matrix of 10 000 examples is 400 MB per file")
     parser_evaluate.add_argument(
         "--decomposition-methods", metavar="METHOD", nargs="+",
         default=_parse_default(defaults["analyses"]["decomposition_method"]),

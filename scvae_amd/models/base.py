@@ -1355,6 +1355,19 @@ class ModelBase:
             raise ValueError(
                 "Distributions need the reconstructed set: "
                 "\"reconstructed\" must be in the output versions.")
+        # (not in the reference's signature) the pairwise distance matrices
+        # of analyse_results' "Distances" (analyses.py:1351-1362), attached
+        # to the returned reconstructed set and to the latent set "z" as
+        # ``distance_matrices``
+        with_distances = kwargs.get("distances")
+        if with_distances not in (None, False, True):
+            raise ValueError(
+                "Distances `{}` not found: None, False or True.".format(
+                    with_distances))
+        if with_distances and "reconstructed" not in output_versions:
+            raise ValueError(
+                "Distances need the reconstructed set: "
+                "\"reconstructed\" must be in the output versions.")
 
         minibatch_size = self._training_minibatch_size(
             minibatch_size, "evaluation")
@@ -1499,6 +1512,18 @@ class ModelBase:
                 preprocessed=bool(evaluation_set.preprocessing_methods))
             distributions_duration = time() - distributions_time_start
 
+        distance_matrices = None
+        if with_distances and master:
+            # over p_x_mean where it lies, before its copy to the host, and
+            # over the z latent values (analyses.py:1351-1362)
+            from scvae_amd.analyses.distances import evaluation_distances
+            distance_matrices = evaluation_distances(
+                outputs["p_x_mean"],
+                latent_z=(evaluation["latent_values"]
+                          if "latent" in output_versions else None),
+                labels=evaluation_set.labels,
+                example_names=evaluation_set.example_names)
+
         output_sets = [None] * len(output_versions)
         if "transformed" in output_versions:
             # (va:2135-2158: the binarised / noisily preprocessed values the
@@ -1538,6 +1563,10 @@ class ModelBase:
                 reconstructed_set.distributions = distributions
                 reconstructed_set.distributions_duration = (
                     distributions_duration)
+            if distance_matrices is not None:
+                output_sets[output_versions.index(
+                    "reconstructed")].distance_matrices = (
+                        distance_matrices["reconstructed"])
             for name, decomposition in decompositions.items():
                 setattr(output_sets[output_versions.index("reconstructed")],
                         name, decomposition)
@@ -1548,6 +1577,8 @@ class ModelBase:
             latent_sets = self._latent_evaluation_sets(
                 evaluation, wrap, latent_names)
             output_sets[output_versions.index("latent")] = latent_sets
+            if distance_matrices is not None and "z" in latent_sets:
+                latent_sets["z"].distance_matrices = distance_matrices["z"]
         self._attach_predictions(output_sets, evaluation, evaluation_set)
         if len(output_sets) == 1:
             output_sets = output_sets[0]
