@@ -432,19 +432,36 @@ int scvae_adam_clip_step(float* theta, float* grad, float* m, float* v, int64_t 
                          void* stream);
 
 /* ---- individual ops (also used by the tests) ---- */
-/* dense_layer (scvae/models/utilities.py:38-76): C (+)= act(op(A) op(B) + bias) */
+/* dense_layer (scvae/models/utilities.py:38-76): C (+)= act(op(A) op(B) + bias)
+ * op(A) is [M, K] (A stored [K, M] with trans_a), op(B) is [K, N] (B stored [N, K] with trans_b).
+ * K = 0 is the empty sum: C = act(bias), or C0 + act(bias) with accumulate.
+ * relu: max(v, 0) of every number; a NaN pre-activation stays NaN (in every kernel and split-K
+ * reducer of this entry and of the count products below).
+ * Refused with -1, nothing launched and C untouched: any of M, N, K, lda, ldb, ldc negative or
+ * above INT32_MAX; a leading dimension below the extent of its rows (lda < K, or < M with
+ * trans_a; ldb < N, or < K with trans_b; ldc < N).
+ * A null workspace (or one too small for the slabs) runs the product unsplit. */
 int scvae_gemm(int32_t trans_a, int32_t trans_b, const float* A, const float* B,
                const float* bias, float* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                int64_t ldb, int64_t ldc, int32_t relu, int32_t accumulate, void* workspace,
                int64_t workspace_bytes, void* stream);
 int64_t scvae_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+/* Which launches scvae_gemm makes for a shape (host code, nothing is launched; the function is
+ * the dispatcher scvae_gemm itself calls).  out[0]: the kernel, 0 = 64x64 tiles, 1 = 128x128
+ * tiles, 2 = the narrow-N kernel; out[1]: the number of split-K slabs after rounding (1 = unsplit);
+ * out[2]: k per slab; out[3]: the reducer, 0 = none, 1 = slab order, 2 = the wide one for many
+ * slabs of a small C.  workspace_bytes: what the call would pass, 0 for a null workspace. */
+int scvae_gemm_route(int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t K,
+                     int64_t ldb, int64_t workspace_bytes, int32_t out[4]);
 /* The same dense layer when its input is the count matrix itself (mu:53-59 on
  * x_train[idx].toarray(), va:997-998), x integers in [0, 65536):
  *   mode 0: C[rows, N] = act(x[rows, cols] other[cols, N] + bias)   (x W + b)
  *   mode 1: C[cols, N] = x[rows, cols]^T other[rows, N]             (dW = x^T dA)
  * exact hi/lo bf16 cut of x times an exact three-term bf16 split of `other`, fp32 accumulation
  * on the bf16 matrix cores; N <= 128.  workspace: scvae_count_gemm_workspace_bytes (16-byte
- * aligned).  The precondition on x is the caller's (scvae_check_counts). */
+ * aligned).  The precondition on x is the caller's (scvae_check_counts).
+ * Refused with -1, nothing launched and C untouched (all three entries): ldx, rows, cols,
+ * ld_other, N or ldc negative or above INT32_MAX; ldx < cols, ld_other < N or ldc < N. */
 int scvae_count_gemm(int32_t mode, const float* x, int64_t ldx, int64_t rows, int64_t cols,
                      const float* other, int64_t ld_other, int64_t N, const float* bias,
                      int32_t relu, float* C, int64_t ldc, void* workspace, int64_t workspace_bytes,
@@ -455,7 +472,26 @@ int scvae_count_gemm_u16(int32_t mode, const uint16_t* x, int64_t ldx, int64_t r
                          const float* other, int64_t ld_other, int64_t N, const float* bias,
                          int32_t relu, float* C, int64_t ldc, void* workspace,
                          int64_t workspace_bytes, void* stream);
+/* scvae_count_gemm_u16 with x a resident matrix of pitch ldx: row m of the product's x is its
+ * row x_rows[m] (device, [rows], 64-bit, any order, rows may repeat) -- bit-identical to
+ * scvae_count_gemm_u16 on the gathered rows */
+int scvae_count_gemm_u16_rows(int32_t mode, const uint16_t* x, int64_t ldx, int64_t rows,
+                              int64_t cols, const float* other, int64_t ld_other, int64_t N,
+                              const float* bias, int32_t relu, float* C, int64_t ldc,
+                              void* workspace, int64_t workspace_bytes, const int64_t* x_rows,
+                              void* stream);
 int64_t scvae_count_gemm_workspace_bytes(int32_t mode, int64_t rows, int64_t cols, int64_t N);
+/* Which launches the three count entries make for a shape (host code, nothing is launched; the
+ * dispatcher they call).  out[0]: k_main, the part of the contraction on the matrix cores (whole
+ * chunks of 32, mode 1: 16; the rest is added by the reducer); out[1]: split-K slabs after
+ * rounding (0 where k_main = 0: the reducer does the whole product); out[2]: k per slab;
+ * out[3]: 1 = the kernel stores C itself, no reducer; out[4]: column tiles per wave -- NQ (1, 2)
+ * in mode 0, NT (1..4) in mode 1; out[5]: 1 = the gene-pair weight-gradient kernel (uint16 x, an
+ * even number of genes); out[6]: waves per workgroup of the main kernel (0 where k_main = 0);
+ * out[7]: 0 (reserved).  indexed: the call goes through scvae_count_gemm_u16_rows (the same
+ * geometries, x read through the index). */
+int scvae_count_gemm_route(int32_t mode, int64_t rows, int64_t cols, int64_t N, int32_t x_is_u16,
+                           int32_t indexed, int32_t out[8]);
 /* *bad (device int32) = 1 unless every one of the n values is an integer in [0, 65536) */
 int scvae_check_counts(const float* values, int64_t n, int32_t* bad, void* stream);
 /* p(x|z).log_prob(t) summed over F (va:2583-2590); pre = heads' pre-activations [rows,F] */

@@ -214,6 +214,14 @@ SIGNATURES = {
         c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32,
         c_void_p, c_int64, c_void_p]),
     "scvae_gemm_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "scvae_gemm_route": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, c_int64,
+                                   c_int64, c_void_p]),
+    "scvae_count_gemm_route": (c_int32, [c_int32, c_int64, c_int64, c_int64, c_int32, c_int32,
+                                         c_void_p]),
+    "scvae_count_gemm_u16_rows": (c_int32, [
+        c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64,
+        c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+        c_void_p, c_void_p]),
     "scvae_loglik_fwd": (c_int32, [
         c_int32, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_int64,
         c_int64, c_int64, c_void_p]),

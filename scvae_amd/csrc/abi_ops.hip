@@ -3,6 +3,10 @@
 // kernels, minibatch fetch, batch-norm pieces, noise.  The plan's entries are in plan.hip.
 #include "plan.hpp"   // (count_tiles_of; no entry here takes a scvae_plan)
 
+// every extent and leading dimension of the GEMM entries is narrowed to int: refuse what does not
+// fit before the cast
+static inline bool fits_int(int64_t v) { return v >= 0 && v <= INT32_MAX; }
+
 extern "C" {
 
 int scvae_adam_clip_step(float* theta, float* grad, float* m, float* v, int64_t n,
@@ -16,6 +20,9 @@ int scvae_adam_clip_step(float* theta, float* grad, float* m, float* v, int64_t 
 int scvae_gemm(int32_t ta, int32_t tb, const float* A, const float* B, const float* bias, float* C,
                int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t relu,
                int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
+  SCVAE_ARG(fits_int(M) && fits_int(N) && fits_int(K) && fits_int(lda) && fits_int(ldb) &&
+            fits_int(ldc) && workspace_bytes >= 0);
+  SCVAE_ARG(lda >= (ta ? M : K) && ldb >= (tb ? K : N) && ldc >= N);
   return scvae::gemm((hipStream_t)stream, ta != 0, tb != 0, A, B, bias, C, (int)M, (int)N, (int)K,
                      (int)lda, (int)ldb, (int)ldc, relu ? scvae::ACT_RELU : scvae::ACT_NONE,
                      accumulate != 0, (float*)workspace, (size_t)workspace_bytes);
@@ -25,6 +32,9 @@ int scvae_count_gemm(int32_t mode, const float* x, int64_t ldx, int64_t rows, in
                      int32_t relu, float* C, int64_t ldc, void* workspace, int64_t workspace_bytes,
                      void* stream) {
   SCVAE_ARG(workspace_bytes >= 0);
+  SCVAE_ARG(fits_int(ldx) && fits_int(rows) && fits_int(cols) && fits_int(ld_other) &&
+            fits_int(N) && fits_int(ldc));
+  SCVAE_ARG(ldx >= cols && ld_other >= N && ldc >= N);
   return scvae::count_gemm((hipStream_t)stream, mode, x, (int)ldx, (int)rows, (int)cols, other,
                            (int)ld_other, (int)N, bias, relu ? scvae::ACT_RELU : scvae::ACT_NONE,
                            C, (int)ldc, workspace, (size_t)workspace_bytes);
@@ -36,6 +46,25 @@ int64_t scvae_count_gemm_workspace_bytes(int32_t mode, int64_t rows, int64_t col
 int scvae_check_counts(const float* values, int64_t n, int32_t* bad, void* stream) {
   SCVAE_ARG(n >= 0);
   return scvae::check_counts((hipStream_t)stream, values, (size_t)n, bad);
+}
+int scvae_gemm_route(int32_t ta, int32_t tb, int64_t M, int64_t N, int64_t K, int64_t ldb,
+                     int64_t workspace_bytes, int32_t out[4]) {
+  SCVAE_ARG(out && fits_int(M) && fits_int(N) && fits_int(K) && fits_int(ldb) &&
+            workspace_bytes >= 0);
+  const scvae::GemmRoute r = scvae::gemm_route(ta != 0, tb != 0, (int)M, (int)N, (int)K, (int)ldb,
+                                               (size_t)workspace_bytes);
+  out[0] = r.kernel; out[1] = r.splits; out[2] = r.k_chunk; out[3] = r.reducer;
+  return 0;
+}
+int scvae_count_gemm_route(int32_t mode, int64_t rows, int64_t cols, int64_t N, int32_t x_is_u16,
+                           int32_t indexed, int32_t out[8]) {
+  SCVAE_ARG(out && (mode == 0 || mode == 1) && fits_int(rows) && fits_int(cols) && fits_int(N));
+  SCVAE_ARG(scvae::count_gemm_supported((int)N) && (!indexed || x_is_u16));
+  const scvae::CountGemmRoute r = scvae::count_gemm_route(mode, (int)rows, (int)cols, (int)N,
+                                                          x_is_u16 != 0, indexed != 0);
+  out[0] = r.k_main; out[1] = r.splits; out[2] = r.k_chunk; out[3] = r.direct;
+  out[4] = r.tiles; out[5] = r.pair; out[6] = r.waves; out[7] = 0;
+  return 0;
 }
 int64_t scvae_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   return (int64_t)scvae::gemm_workspace_bytes((int)M, (int)N, (int)K);
@@ -194,10 +223,28 @@ int scvae_count_gemm_u16(int32_t mode, const uint16_t* x, int64_t ldx, int64_t r
                          int32_t relu, float* C, int64_t ldc, void* workspace,
                          int64_t workspace_bytes, void* stream) {
   SCVAE_ARG(workspace_bytes >= 0);
+  SCVAE_ARG(fits_int(ldx) && fits_int(rows) && fits_int(cols) && fits_int(ld_other) &&
+            fits_int(N) && fits_int(ldc));
+  SCVAE_ARG(ldx >= cols && ld_other >= N && ldc >= N);
   return scvae::count_gemm_u16((hipStream_t)stream, mode, x, (int)ldx, (int)rows, (int)cols, other,
                                (int)ld_other, (int)N, bias,
                                relu ? scvae::ACT_RELU : scvae::ACT_NONE, C, (int)ldc, workspace,
                                (size_t)workspace_bytes);
+}
+
+int scvae_count_gemm_u16_rows(int32_t mode, const uint16_t* x, int64_t ldx, int64_t rows,
+                              int64_t cols,
+                              const float* other, int64_t ld_other, int64_t N, const float* bias,
+                              int32_t relu, float* C, int64_t ldc, void* workspace,
+                              int64_t workspace_bytes, const int64_t* x_rows, void* stream) {
+  SCVAE_ARG(workspace_bytes >= 0 && x_rows);
+  SCVAE_ARG(fits_int(ldx) && fits_int(rows) && fits_int(cols) && fits_int(ld_other) &&
+            fits_int(N) && fits_int(ldc));
+  SCVAE_ARG(ldx >= cols && ld_other >= N && ldc >= N);
+  return scvae::count_gemm_u16((hipStream_t)stream, mode, x, (int)ldx, (int)rows, (int)cols, other,
+                               (int)ld_other, (int)N, bias,
+                               relu ? scvae::ACT_RELU : scvae::ACT_NONE, C, (int)ldc, workspace,
+                               (size_t)workspace_bytes, x_rows);
 }
 
 int64_t scvae_count_tiles_padded(int64_t F) {

@@ -275,6 +275,33 @@ static bool cf_two_roles() {
   return on;
 }
 
+CountGemmRoute count_gemm_route(int mode, int rows, int cols, int N, bool x_is_u16, bool indexed) {
+  (void)indexed;                              // (the same geometries, read through the row index)
+  const int M = mode == 0 ? rows : cols, K = mode == 0 ? cols : rows;
+  const int bk = cg_bk(mode);
+  CountGemmRoute r = {K / bk * bk, 0, 0, 0, 0, 0, 0};
+  if (r.k_main == 0) return r;                // the reduce kernel does the whole product
+  int splits = cg_splits(mode, M, r.k_main);
+  r.k_chunk = r.k_main;
+  if (splits > 1) {
+    r.k_chunk = (r.k_main + splits - 1) / splits;
+    r.k_chunk = (r.k_chunk + bk - 1) / bk * bk;
+    splits = (r.k_main + r.k_chunk - 1) / r.k_chunk;
+  }
+  r.splits = splits;
+  r.direct = mode == 0 && splits == 1 && r.k_main == K;
+  const int NT = (N + 31) / 32;
+  if (mode == 0) {
+    r.tiles = NT > 2 ? 2 : 1;
+    r.waves = 8;
+  } else {
+    r.tiles = NT;
+    r.pair = x_is_u16 && (M & 1) == 0;
+    r.waves = r.pair ? cd_waves(M, r.k_main) : 4;      // (8: the pair kernel)
+  }
+  return r;
+}
+
 template <typename XT>
 static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, int rows, int cols,
                            const float* other, int ld_other, int N, const float* bias, int act,
@@ -291,33 +318,27 @@ static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, i
   SCVAE_ARG(((uintptr_t)workspace & 15) == 0);
   const int M = mode == 0 ? rows : cols, K = mode == 0 ? cols : rows;
   const int bk = cg_bk(mode);
-  const int k_main = K / bk * bk;            // whole chunks: matrix cores; the rest: reduction
+  const CountGemmRoute route = count_gemm_route(mode, rows, cols, N, sizeof(XT) == 2, xrows != nullptr);
+  const int k_main = route.k_main;           // whole chunks: matrix cores; the rest: reduction
   const int Kpad = cg_kpad(K);
   uint16_t* T = reinterpret_cast<uint16_t*>(workspace);
   const size_t t_bytes = ((size_t)3 * CG_NP * Kpad * sizeof(uint16_t) + 255) / 256 * 256;
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + t_bytes);
-  int splits = 0;
+  const int splits = route.splits;
   if (k_main > 0) {
     hipLaunchKernelGGL(split3_transpose_kernel, dim3((Kpad / 8 + 1) / 2), dim3(256), 0, stream,
                        other, K, N, ld_other, T, Kpad, bk);
     SCVAE_LAUNCH_CHECK("split3_transpose_kernel");
-    splits = cg_splits(mode, M, k_main);
-    int k_chunk = k_main;
-    if (splits > 1) {
-      k_chunk = (k_main + splits - 1) / splits;
-      k_chunk = (k_chunk + bk - 1) / bk * bk;
-      splits = (k_main + k_chunk - 1) / k_chunk;
-    }
+    const int k_chunk = route.k_chunk;
     // a single split with no leftover terms writes C directly (bias and activation included)
-    const bool direct = mode == 0 && splits == 1 && k_main == K;
+    const bool direct = route.direct != 0;
     float* dst = direct ? C : slabs;
     const int ldo = direct ? ldc : N;
-    const int NT = (N + 31) / 32;
     const float* kbias = direct ? bias : nullptr;
     const int kact = direct ? act : (int)ACT_NONE, kdirect = direct ? 1 : 0;
     if (mode == 0) {
       const dim3 grid((M + CF_BM - 1) / CF_BM, splits);
-      const int NQ = NT > 2 ? 2 : 1;
+      const int NQ = route.tiles;
       const size_t lds = cf_lds_bytes(NQ);
 #define SCVAE_CF(NQ_)                                                                             \
   do {                                                                                            \
@@ -354,13 +375,14 @@ static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, i
 #undef SCVAE_CF2
 #undef SCVAE_CF
     } else {
-      const int nw = (sizeof(XT) == 2 && (M & 1) == 0) ? cd_waves(M, k_main) : 4;   // (8: the pair kernel)
+      const int nw = route.waves, NT = route.tiles;
+      const bool pair = route.pair != 0;     // gene pairs per lane (4-byte loads)
       const dim3 grid((M + nw * CG_TM - 1) / (nw * CG_TM), splits);
 #define SCVAE_CD(NT_)                                                                             \
   do {                                                                                            \
     if constexpr (sizeof(XT) == 2) {                                                              \
       if (xrows) {          /* x through a row index: the same geometries, indexed */             \
-        if ((M & 1) != 0)                                                                         \
+        if (!pair)                                                                                \
           hipLaunchKernelGGL((count_gemm_dw_rows_kernel<NT_, false, 4>), grid, dim3(256), 0,      \
                              stream, x, ldx, M, k_main, T, Kpad, N, k_chunk, dst, ldo, xrows);    \
         else if (nw == 8)                                                                         \
@@ -371,7 +393,7 @@ static int count_gemm_impl(hipStream_t stream, int mode, const XT* x, int ldx, i
                              stream, x, ldx, M, k_main, T, Kpad, N, k_chunk, dst, ldo, xrows);    \
         break;                                                                                    \
       }                                                                                           \
-      if ((M & 1) == 0) {   /* gene pairs per lane (4-byte loads) */                               \
+      if (pair) {                                                                                 \
         if (nw == 8)                                                                              \
           hipLaunchKernelGGL((count_gemm_dw_kernel<NT_, XT, true, false, 8>), grid, dim3(512), 0, \
                              stream, x, ldx, M, k_main, T, Kpad, N, k_chunk, dst, ldo);           \
@@ -839,7 +861,7 @@ __global__ __launch_bounds__(512) void count_fwd2_kernel(
           const int m = m0 + row0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * kg;
           if (m < M) {
             float v = acc[t][q][r] + bv;
-            if (direct && act == ACT_RELU) v = fmaxf(v, 0.f);
+            if (direct && act == ACT_RELU) v = relu_keep_nan(v);
             dst[(size_t)m * ldo + col] = v;
           }
         }

@@ -218,7 +218,7 @@
         const int m = m0 + 64 * rg + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * kg;
         if (m < M) {
           float v = acc[t][q][r] + bv;
-          if (direct && act == ACT_RELU) v = fmaxf(v, 0.f);
+          if (direct && act == ACT_RELU) v = relu_keep_nan(v);
           dst[(size_t)m * ldo + col] = v;
         }
       }

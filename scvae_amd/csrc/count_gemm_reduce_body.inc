@@ -24,6 +24,6 @@
       s = fmaf(xv, other[(size_t)k * ld_other + col], s);
     }
     if (bias) s += bias[col];
-    if (act == ACT_RELU) s = fmaxf(s, 0.f);
+    if (act == ACT_RELU) s = relu_keep_nan(s);
     C[(size_t)row * ldc + col] = s;
   }

@@ -3,7 +3,8 @@
 // This is the dense layer of scvae/models/utilities.py:38-76
 // (tf.contrib.layers.fully_connected: x*W + b, optional ReLU) and its two
 // backward contractions (dX = dY*W^T, dW = X^T*dY).  fp32 in, fp32 accumulate:
-// the MFMA result is bit-identical to a k-ordered fmaf chain.
+// the MFMA result is bit-identical to a k-ordered fmaf chain.  K = 0 is the empty sum:
+// C = act(bias), or C0 + act(bias) with accumulate.  ReLU keeps a NaN (relu_keep_nan).
 //
 // Tile: 64x64 per 256-thread workgroup (4 waves, one 32x32 accumulator each),
 // BK = 16, operands staged k-major in LDS so that the MFMA A/B fragment reads
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(
       slabs[((size_t)kz * M + row) * N + col] = acc[r];
     } else {
       float v = acc[r] + bv;
-      if (act == ACT_RELU) v = fmaxf(v, 0.f);
+      if (act == ACT_RELU) v = relu_keep_nan(v);
       float* c = C + (size_t)row * ldc + col;
       *c = accumulate ? (*c + v) : v;
     }
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(
         slabs[((size_t)kz * M + row) * N + col] = acc[q][r];
       } else {
         float v = acc[q][r] + bv;
-        if (act == ACT_RELU) v = fmaxf(v, 0.f);
+        if (act == ACT_RELU) v = relu_keep_nan(v);
         float* c = C + (size_t)row * ldc + col;
         *c = accumulate ? (*c + v) : v;
       }
@@ -370,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void gemm_narrow_kernel(
       slabs[((size_t)kz * M + row) * N + col] = v;
     } else {
       if (bias != nullptr) v += bias[col];
-      if (act == ACT_RELU) v = fmaxf(v, 0.f);
+      if (act == ACT_RELU) v = relu_keep_nan(v);
       float* c = C + (size_t)row * ldc + col;
       *c = accumulate ? (*c + v) : v;
     }
@@ -401,7 +402,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(
     float s = 0.f;
     for (int z = 0; z < splits; ++z) s += slabs[(size_t)z * total + i];
     if (bias) s += bias[col];
-    if (act == ACT_RELU) s = fmaxf(s, 0.f);
+    if (act == ACT_RELU) s = relu_keep_nan(s);
     float* c = C + (size_t)row * ldc + col;
     *c = accumulate ? (*c + s) : s;
   }
@@ -436,7 +437,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(
     for (int q = 0; q < 16; ++q) t += red[q][il];
     const int row = (int)(i / N), col = (int)(i % N);
     if (bias) t += bias[col];
-    if (act == ACT_RELU) t = fmaxf(t, 0.f);
+    if (act == ACT_RELU) t = relu_keep_nan(t);
     float* c = C + (size_t)row * ldc + col;
     *c = accumulate ? (*c + t) : t;
   }
@@ -488,17 +489,15 @@ int gemm_choose_splits(int M, int N, int K) {
   return (int)s;
 }
 
-int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, const float* bias,
-         float* C, int M, int N, int K, int lda, int ldb, int ldc, int act, bool accumulate,
-         float* workspace, size_t workspace_bytes) {
-  SCVAE_ARG(A && B && C);
-  SCVAE_ARG(M >= 0 && N >= 0 && K >= 0);
-  if (M == 0 || N == 0) return 0;
+GemmRoute gemm_route(bool ta, bool tb, int M, int N, int K, int ldb, size_t workspace_bytes) {
+  (void)ta;                                   // (a template argument of every kernel, no route)
+  GemmRoute r = {0, 1, K, 0};
   const bool big = gemm_use_big(tb, M, N, K);
   // N = 32 q + r with r <= 8 (e.g. the default hidden size 100): no padding of N
   const bool narrow = big && N >= 32 && N <= NBN && (N % 32) != 0 && (N % 32) <= 8 && ldb >= N;
+  r.kernel = narrow ? 2 : big ? 1 : 0;
+  int splits = 1;
   if (narrow) {
-    int splits = 1;
     const long tiles = (M + NBM - 1) / NBM;
     if (tiles < 384) {
       // two workgroups per CU in total (a 1.5-wave grid costs more than it gains)
@@ -507,18 +506,35 @@ int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, c
       if (splits < 1) splits = 1;
       if (splits > 64) splits = 64;
     }
-    if (splits > 1 && (workspace == nullptr ||
-                       workspace_bytes < (size_t)splits * M * N * sizeof(float)))
-      splits = 1;
-    int k_chunk = K;
-    if (splits > 1) {
-      k_chunk = (K + splits - 1) / splits;
-      k_chunk = (k_chunk + NBK - 1) / NBK * NBK;
-      splits = (K + k_chunk - 1) / k_chunk;
-    }
+  } else {
+    splits = big ? gemm_big_splits(M, N, K) : gemm_choose_splits(M, N, K);
+  }
+  if (splits > 1 && workspace_bytes < (size_t)splits * M * N * sizeof(float)) splits = 1;
+  const int kstep = narrow ? NBK : big ? BBK : GBK;
+  if (splits > 1) {
+    int k_chunk = (K + splits - 1) / splits;
+    k_chunk = (k_chunk + kstep - 1) / kstep * kstep;
+    r.k_chunk = k_chunk;
+    splits = (K + k_chunk - 1) / k_chunk;
+  }
+  r.splits = splits;
+  if (splits > 1)
+    r.reducer = (!narrow && splits >= 16 && (size_t)M * N <= (size_t)1 << 16) ? 2 : 1;
+  return r;
+}
+
+int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, const float* bias,
+         float* C, int M, int N, int K, int lda, int ldb, int ldc, int act, bool accumulate,
+         float* workspace, size_t workspace_bytes) {
+  SCVAE_ARG(A && B && C);
+  SCVAE_ARG(M >= 0 && N >= 0 && K >= 0);
+  if (M == 0 || N == 0) return 0;
+  const GemmRoute route = gemm_route(ta, tb, M, N, K, ldb, workspace ? workspace_bytes : 0);
+  const int splits = route.splits, k_chunk = route.k_chunk;
+  float* slabs = splits > 1 ? workspace : nullptr;
+  const int acc = accumulate ? 1 : 0;
+  if (route.kernel == 2) {
     dim3 grid(1, (M + NBM - 1) / NBM, splits);
-    float* slabs = splits > 1 ? workspace : nullptr;
-    const int acc = accumulate ? 1 : 0;
     if (ta)
       hipLaunchKernelGGL((gemm_narrow_kernel<true>), grid, dim3(512), 0, stream, A, B, bias, C, M,
                          N, K, lda, ldb, ldc, act, acc, k_chunk, slabs);
@@ -526,32 +542,8 @@ int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, c
       hipLaunchKernelGGL((gemm_narrow_kernel<false>), grid, dim3(512), 0, stream, A, B, bias, C, M,
                          N, K, lda, ldb, ldc, act, acc, k_chunk, slabs);
     SCVAE_LAUNCH_CHECK("gemm_narrow_kernel");
-    if (splits > 1) {
-      const size_t total = (size_t)M * N;
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 2048) blocks = 2048;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, slabs, bias, C,
-                         M, N, ldc, splits, act, acc);
-      SCVAE_LAUNCH_CHECK("splitk_reduce_kernel");
-    }
-    return 0;
-  }
-  int splits = big ? gemm_big_splits(M, N, K) : gemm_choose_splits(M, N, K);
-  if (splits > 1 && (workspace == nullptr ||
-                     workspace_bytes < (size_t)splits * M * N * sizeof(float)))
-    splits = 1;
-  const int kstep = big ? BBK : GBK;
-  const int tile = big ? BT : GT;
-  int k_chunk = K;
-  if (splits > 1) {
-    k_chunk = (K + splits - 1) / splits;
-    k_chunk = (k_chunk + kstep - 1) / kstep * kstep;
-    splits = (K + k_chunk - 1) / k_chunk;
-  }
-  dim3 grid((N + tile - 1) / tile, (M + tile - 1) / tile, splits);
-  float* slabs = splits > 1 ? workspace : nullptr;
-  const int acc = accumulate ? 1 : 0;
-  if (big) {
+  } else if (route.kernel == 1) {
+    dim3 grid((N + BT - 1) / BT, (M + BT - 1) / BT, splits);
     if (ta)
       hipLaunchKernelGGL((gemm_big_kernel<true>), grid, dim3(512), 0, stream, A, B, bias, C, M, N, K,
                          lda, ldb, ldc, act, acc, k_chunk, slabs);
@@ -560,6 +552,7 @@ int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, c
                          K, lda, ldb, ldc, act, acc, k_chunk, slabs);
     SCVAE_LAUNCH_CHECK("gemm_big_kernel");
   } else {
+    dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT, splits);
 #define SCVAE_GEMM_LAUNCH(TA_, TB_)                                                              \
   hipLaunchKernelGGL((gemm_kernel<TA_, TB_>), grid, dim3(256), 0, stream, A, B, bias, C, M, N, K, \
                      lda, ldb, ldc, act, acc, k_chunk, slabs)
@@ -568,11 +561,11 @@ int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, c
 #undef SCVAE_GEMM_LAUNCH
     SCVAE_LAUNCH_CHECK("gemm_kernel");
   }
-  if (splits > 1) {
+  if (route.reducer != 0) {
     const size_t total = (size_t)M * N;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 2048) blocks = 2048;
-    if (splits >= 16 && total <= (size_t)1 << 16) {
+    if (route.reducer == 2) {
       hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256),
                          0, stream, slabs, bias, C, M, N, ldc, splits, act, acc);
     } else {

@@ -10,7 +10,16 @@ namespace scvae {
 
 enum Activation : int { ACT_NONE = 0, ACT_RELU = 1 };
 
+// ReLU of the GEMM epilogues.  fmaxf(v, 0) -- C's and the hardware's max -- returns 0 for a NaN;
+// here a NaN pre-activation stays NaN and every other input gives exactly fmaxf's result.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // ---- gemm.hip ----
+// What gemm() launches for a shape (the dispatcher itself: gemm() calls it).  kernel: 0 the 64-tile
+// kernel, 1 the 128-tile kernel, 2 the narrow-N kernel; splits and k_chunk after rounding;
+// reducer: 0 none, 1 slab, 2 wide.  workspace_bytes: 0 for a null workspace.
+struct GemmRoute { int kernel, splits, k_chunk, reducer; };
+GemmRoute gemm_route(bool ta, bool tb, int M, int N, int K, int ldb, size_t workspace_bytes);
 int gemm_choose_splits(int M, int N, int K);
 size_t gemm_workspace_bytes(int M, int N, int K);
 int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, const float* bias,
@@ -23,6 +32,12 @@ int gemm(hipStream_t stream, bool ta, bool tb, const float* A, const float* B, c
 // mode 0: C[rows, N] = x[rows, cols] other[cols, N] + bias;  mode 1: C[cols, N] = x^T other[rows, N]
 bool count_gemm_supported(int N);
 size_t count_gemm_workspace_bytes(int mode, int rows, int cols, int N);
+// What count_gemm / count_gemm_u16 launch for a shape (the dispatcher itself).  k_main: the part
+// of the contraction on the matrix cores; splits (0 where k_main == 0) and k_chunk after rounding;
+// direct: the kernel stores C itself; tiles: NQ (mode 0) or NT (mode 1); pair: the gene-pair
+// weight-gradient kernel; waves: per workgroup of the main kernel (0 where k_main == 0).
+struct CountGemmRoute { int k_main, splits, k_chunk, direct, tiles, pair, waves; };
+CountGemmRoute count_gemm_route(int mode, int rows, int cols, int N, bool x_is_u16, bool indexed);
 int count_gemm(hipStream_t stream, int mode, const float* x, int ldx, int rows, int cols,
                const float* other, int ld_other, int N, const float* bias, int act, float* C,
                int ldc, void* workspace, size_t workspace_bytes);
